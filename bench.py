@@ -16,7 +16,8 @@ all-reduce per step, overlapped on a side stream).
 Launch (the reference's `mpirun -np P ./riemann`, riemann.cpp:62-86: one command, P ranks,
 one gathered result):
 
-    python bench.py                          # 1 GPU, in this process
+    python bench.py                          # 1 GPU, in this process: the headline only
+    python bench.py --full                   # ... and every extra measurement after it
     python bench.py --gpus 8                 # spawns 8 rank processes (one per GPU)
     torchrun --nproc-per-node 8 bench.py --gpus 8     # the same ranks under torchrun
 
@@ -33,7 +34,10 @@ profiles/r6/batch_tail.md). The JSON line reports all of these as "warmup_settle
 
 Scaling: the headline is strong (N = 1e9 in total; --scaling weak makes --samples a per-GPU
 count instead). The results of the last batch of timed steps (every rank holds the global
-sums) are checked on the host against the rule's closed-form truncation error. After the timed
+sums) are checked on the host against the rule's closed-form truncation error. A plain run
+ends there: it sets up, warms up, times the K steps, writes them out under --dump-outputs DIR
+(result.npy: the last step's value; step_results.npy: every step of the last batch) and
+prints the record. With --full, after the timed
 region (outside it) the same ranks also measure, each with its own graphs, timing and
 pass/fail ("verified"): the weak-scaling form, 1e9 samples PER GPU (N = 1e9 x G,
 "weak_1e9_per_gpu"); the same config with IEEE division per sample ("ieee_div"); the headline
@@ -134,15 +138,23 @@ def parse(argv=None) -> argparse.Namespace:
                    help="one all-reduce per step instead of one per graph batch of steps")
     p.add_argument("--force-collective", action="store_true",
                    help="run the RCCL all-reduce stage even on 1 GPU (tests the multi-GPU graph)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything else the record can "
+                        "carry: the post-timing extras and, on several GPUs, the diagnostic "
+                        "batch and communicator probes (a plain run measures the headline only)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what they computed as DIR/<name>.npy "
+                        "(float64): result.npy, the last timed step's global value, and "
+                        "step_results.npy, the value of every step of the last timed batch")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the post-timing extras (IEEE run, per-point ulp, BASELINE #1, #3, #4, #5, "
-                        "host engine)")
+                   help="with --full: skip the post-timing extras (IEEE run, per-point ulp, "
+                        "BASELINE #1, #3, #4, #5, host engine)")
     p.add_argument("--sweep-gpus", default="",
                    help="e.g. 1,2,4,8: run the scaling sweep (cuda_v_mpi_amd/parallel/scaling.py) "
                         "over these GPU counts instead of one benchmark")
     p.add_argument("--no-diag", action="store_true",
-                   help="skip the untimed diagnostic batch and communicator probes that a "
-                        "multi-rank run records after its timed region (diagnostic_batch)")
+                   help="with --full: skip the untimed diagnostic batch and communicator probes "
+                        "that a multi-rank run records after its timed region (diagnostic_batch)")
     p.add_argument("--diag-allgather-mb", type=float, default=144.0,
                    help="total size of the diagnostic allgather (the reference's 144 MB "
                         "table, 4main.c:157)")
@@ -441,7 +453,10 @@ def main(argv=None) -> int:
     ms_per_step = elapsed_max / args.steps * 1e3
     value = n_total * args.steps / elapsed_max
 
-    # ---- outside the timed region: transport facts and the extras
+    if args.dump_outputs and ctx.is_root:
+        dump_outputs(args.dump_outputs, vals)
+
+    # ---- outside the timed region: transport facts and, with --full, the extras
     comm = getattr(integ, "_comm", None)
     rccl_world = comm.transport_world if comm is not None else None
     rccl_version = None
@@ -465,7 +480,7 @@ def main(argv=None) -> int:
     if transport_error:
         print(f"bench.py: {transport_error}", file=sys.stderr)
     diag = None
-    if world > 1 and not args.no_diag:
+    if args.full and world > 1 and not args.no_diag:
         # untimed, after the timed region: where a multi-GPU step's time went
         try:
             diag = batch_diagnostics(args, ctx, integ, plan, dev, cpu, use_torch, transport)
@@ -474,7 +489,7 @@ def main(argv=None) -> int:
             print(f"bench.py: diagnostics failed: {diag['error']}", file=sys.stderr)
     extras = {}
     extras_ok = True
-    if not cpu and not use_torch and not args.no_extras:
+    if args.full and not cpu and not use_torch and not args.no_extras:
         # The headline is already measured: a failure in an extra must not cost the record.
         # (Every rank runs the same extras, so an exception on one is one on all; the
         # collective sequence stays matched.)
@@ -496,6 +511,7 @@ def main(argv=None) -> int:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "warmup_settle_steps": settle_steps,
             # the untimed K-step pattern launched and synced on its own right before the clock
             "warmup_rearm_batch": rearm,
@@ -591,6 +607,18 @@ def main(argv=None) -> int:
                 f.write(json.dumps(out) + "\n")
     ctx.destroy()
     return 0 if ok else 1
+
+
+def dump_outputs(path: str, vals: list[float]) -> None:
+    """What a caller of the timed path receives, as float64 .npy files: the global value of
+    the last timed step (result.npy, shape (1,)) and of every step of the last timed batch,
+    oldest first (step_results.npy). The integrands are analytic or seeded, so two runs with
+    the same arguments integrate the same inputs."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "result.npy"), np.asarray(vals[-1:], dtype=np.float64))
+    np.save(os.path.join(path, "step_results.npy"), np.asarray(vals, dtype=np.float64))
 
 
 def _spread(vals: list[float]) -> dict:

@@ -59,8 +59,9 @@ def _last_json(text: str) -> dict | None:
 
 def run_bench(n: int, steps: int, warmup: int, timeout: float = 900.0,
               extra: list[str] | None = None) -> dict:
+    # --full: the rows' weak / 1e10 / 2-D / one-shot columns come from the record's extras
     cmd = [sys.executable, BENCH, "--gpus", str(n), "--steps", str(steps), "--warmup",
-           str(warmup)] + list(extra or [])
+           str(warmup), "--full"] + list(extra or [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=REPO)
     js = _last_json(p.stdout)
     if p.returncode != 0 or js is None:

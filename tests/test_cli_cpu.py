@@ -121,7 +121,8 @@ def test_bench_diagnostic_batch_cpu():
     timed steps; that 5 % check is the native path's, test_diagnose_batch_accounts_for_the_
     timed_batch on a GPU.)"""
     p = _bench("--gpus", "2", "--device", "cpu", "--backend", "gloo", "--samples", "8e6",
-               "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--diag-allgather-mb", "8",
+               "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--full",
+               "--diag-allgather-mb", "8",
                env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert p.returncode == 0, p.stderr[-3000:]
     js = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -146,6 +147,28 @@ def test_bench_single_gpu_record_has_no_diagnostics():
     assert p.returncode == 0, p.stderr[-3000:]
     js = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert "diagnostic_batch" not in js and js["verified"]
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs DIR: the timed steps' values as float64 .npy (the last step's, and every
+    step of the last batch), the record's `result` among them, identical from run to run; a
+    plain run carries no extras (`full` false)."""
+    import numpy as np
+
+    runs = []
+    for d in ("a", "b"):
+        p = _bench("--device", "cpu", "--samples", "2e4", "--steps", "3", "--warmup", "1",
+                   "--settle-ms", "0", "--dump-outputs", str(tmp_path / d))
+        assert p.returncode == 0, p.stderr[-3000:]
+        js = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert js["full"] is False and js["steps"] == 3 and js["ms_per_step"] > 0
+        assert sorted(f.name for f in (tmp_path / d).iterdir()) == ["result.npy",
+                                                                    "step_results.npy"]
+        r, s = np.load(tmp_path / d / "result.npy"), np.load(tmp_path / d / "step_results.npy")
+        assert r.dtype == s.dtype == np.float64 and r.shape == (1,) and s.shape == (3,)
+        assert r[0] == s[-1] == js["result"]
+        runs.append((r, s))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
 
 
 def test_bench_spawn_propagates_rank_failure():

@@ -567,7 +567,7 @@ def _torchrun(nproc, args, timeout=300):
 
 def test_bench_torchrun_single_rank(native, cuda):
     p = _torchrun(1, [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "16",
-                      "--warmup", "2"])
+                      "--warmup", "2", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     js = json.loads(p.stdout.strip().splitlines()[-1])
     assert js["verified"] and js["n_gpus"] == 1
@@ -604,7 +604,8 @@ def test_bench_force_collective_graph(native, cuda, bucket):
     """The 1-rank RCCL stage with the multi-step batches replayed as hipGraphs
     (--graph-batches; the default launches them directly, test_bench_contract)."""
     p = _run(["python", os.path.join(REPO, "bench.py"), "--steps", "40", "--warmup", "8",
-              "--force-collective", "--graph-batches"] + ([] if bucket else ["--no-bucket"]))
+              "--full", "--force-collective", "--graph-batches"]
+             + ([] if bucket else ["--no-bucket"]))
     assert p.returncode == 0, p.stderr[-2000:]
     js = json.loads(p.stdout.strip().splitlines()[-1])
     bad = [k for k, v in js.items() if isinstance(v, dict) and v.get("verified") is False]
@@ -616,7 +617,8 @@ def test_bench_force_collective_graph(native, cuda, bucket):
 
 
 def test_bench_contract(native, cuda):
-    p = _run(["python", os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "3"])
+    p = _run(["python", os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "3",
+              "--full"])
     assert p.returncode == 0, p.stderr
     js = json.loads(p.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",

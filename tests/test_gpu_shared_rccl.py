@@ -138,7 +138,8 @@ def test_bench_two_ranks_native_rccl_one_gpu(cuda):
     the communicator's 8-byte all-reduce latency and allgather bandwidth, RCCL's channel
     lines)."""
     rec = _records([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "10",
-                    "--warmup", "3", "--no-extras", "--diag-allgather-mb", "16"], timeout=240)
+                    "--warmup", "3", "--full", "--no-extras", "--diag-allgather-mb", "16"],
+                   timeout=240)
     assert len(rec) == 1
     r = rec[0]
     assert r["verified"] and r["n_gpus"] == 2 and r["ranks_share_gpus"]

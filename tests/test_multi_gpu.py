@@ -88,7 +88,7 @@ def test_bench_torchrun_rccl(native, cuda, g, graphs):
     p = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
               f"--nproc-per-node={g}", "--master-addr", "127.0.0.1", "--master-port",
               str(_port()), os.path.join(REPO, "bench.py"), "--gpus", str(g), "--steps", "48",
-              "--warmup", "8"] + (["--graph-batches"] if graphs else []))
+              "--warmup", "8", "--full"] + (["--graph-batches"] if graphs else []))
     assert p.returncode == 0, p.stderr[-3000:]
     js = json.loads(p.stdout.strip().splitlines()[-1])
     assert js["verified"] and js["n_gpus"] == g and js["config"]["N"] == 10**9
@@ -128,7 +128,7 @@ def test_bench_self_spawned_ranks(native, cuda, g):
     if _devices() < g:
         pytest.skip(f"needs {g} HIP devices")
     p = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(g), "--steps", "48",
-              "--warmup", "8"])
+              "--warmup", "8", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     js = json.loads(p.stdout.strip().splitlines()[-1])
     assert js["verified"] and js["n_gpus"] == g and js["launcher"] == "spawn"
