@@ -228,6 +228,22 @@ inline Integrand parse_integrand(const std::string& s) {
   fail("unknown integrand '" + s + "' (sin|pi4|poly|train|table)", __FILE__, __LINE__);
 }
 
+// --slice R/W: rank R's share of a W-rank run (0 <= R < W). False if the flag is absent.
+inline bool parse_slice(const Args& a, int* rank, int* world) {
+  const std::string s = a.str("slice", "");
+  if (s.empty()) return false;
+  char* end = nullptr;
+  const long r = std::strtol(s.c_str(), &end, 10);
+  const bool sep = end != s.c_str() && *end == '/';
+  const char* ws = sep ? end + 1 : end;
+  const long w = sep ? std::strtol(ws, &end, 10) : 0;
+  if (!sep || end == ws || *end != '\0' || r < 0 || w < 1 || r >= w || w > (1 << 20))
+    fail("--slice wants R/W with 0 <= R < W (got '" + s + "')", __FILE__, __LINE__);
+  *rank = static_cast<int>(r);
+  *world = static_cast<int>(w);
+  return true;
+}
+
 inline std::string json_escape(const std::string& s) {
   std::string o;
   for (char c : s) {

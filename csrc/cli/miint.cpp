@@ -3,6 +3,7 @@
 //   ./miint info
 //   ./miint bench [--integrand pi4] [--n 1e9] [--dtype fp64] [--rule left] [--iters 200]
 //                 [--gpus G] [--div series_exact|series|ieee] [--unfused] [--no-graph]      (JSON lines)
+//                 [--slice R/W] [--diagnose] [--timeline FILE]
 //   ./miint sweep [--gpus G]     N in {1e6,1e9,1e10} x dtype {fp64,fp32} x integrand
 //   ./miint table2d [--grid 4096] [--gpus G] [--slice R/W] [--no-graph]
 //                                2-D velocity-field integral (BASELINE #5); timed as
@@ -38,6 +39,7 @@ struct BenchRow {
   int block = 0, grid = 0;  // launch shape of rank 0's plan
   bool multistep = false, close_in_launch = false, allreduce_to_host = false;
   BatchDiag diag;  // --diagnose: rank 0's diagnostic batch (diag.steps == 0 otherwise)
+  std::string timeline_file;  // --timeline: where rank 0's timeline batch was written
   cli::RankFacts facts;
   cli::Topology topo;
 };
@@ -61,8 +63,60 @@ RiemannConfig make_cfg(const std::string& integ, double n, const std::string& dt
   return c;
 }
 
+// One JSON array of unsigned integers as rows of `cols` ([[..],[..]]).
+template <class T>
+void write_rows(std::FILE* f, const std::vector<T>& v, size_t cols) {
+  std::fputc('[', f);
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i % cols == 0) std::fputs(i ? ",[" : "[", f);
+    else std::fputc(',', f);
+    std::fprintf(f, "%llu", static_cast<unsigned long long>(v[i]));
+    if (i % cols == cols - 1) std::fputc(']', f);
+  }
+  std::fputc(']', f);
+}
+
+// --timeline FILE: one JSON object, the BatchTimeline (arrays as nested lists) and the run it
+// belongs to (tools/timeline_report.py reads it). plain_device_us: the same plan's plain
+// batch between two events (--diagnose in the same run; null without), the denominator of
+// the instrument's own cost.
+void write_timeline(const std::string& path, const BatchTimeline& t, const RiemannConfig& cfg,
+                    const std::string& integrand, const std::string& dtype,
+                    const std::string& div, double plain_device_us) {
+  std::FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) fail("--timeline: cannot open " + path + " for writing", __FILE__, __LINE__);
+  std::fprintf(f, "{\"integrand\":\"%s\",\"n\":%llu,", cli::json_escape(integrand).c_str(),
+               static_cast<unsigned long long>(cfg.n));
+  if (cfg.slice_world > 0)
+    std::fprintf(f, "\"slice_of\":[%d,%d],", cfg.slice_rank, cfg.slice_world);
+  else
+    std::fputs("\"slice_of\":null,", f);
+  std::fprintf(f, "\"dtype\":\"%s\",\"div\":\"%s\",", cli::json_escape(dtype).c_str(),
+               cli::json_escape(div).c_str());
+  std::fprintf(f, "\"steps\":%d,\"grid\":%d,\"block\":%d,\"clock_khz\":%d,\"device_us\":%.17g,",
+               t.steps, t.grid, t.block, t.clock_khz, t.device_us);
+  if (plain_device_us > 0) std::fprintf(f, "\"plain_device_us\":%.17g,", plain_device_us);
+  else std::fputs("\"plain_device_us\":null,", f);
+  std::fputs("\"values\":[", f);
+  for (size_t i = 0; i < t.values.size(); ++i)
+    std::fprintf(f, i ? ",%.17g" : "%.17g", t.values[i]);
+  std::fputs("],\n\"stamps\":", f);
+  write_rows(f, t.stamps, static_cast<size_t>(t.steps) + 2);
+  std::fputs(",\n\"shader_clock\":", f);
+  write_rows(f, t.shader_clock, 2);
+  std::fputs(",\n\"hw\":", f);
+  write_rows(f, t.hw, 2);
+  std::fputs("}\n", f);
+  if (std::fclose(f) != 0) fail("--timeline: writing " + path + " failed", __FILE__, __LINE__);
+}
+
+struct TimelineRequest {
+  std::string file, integrand, dtype, div;  // empty file: no timeline
+};
+
 BenchRow bench_one(const cli::Topology& topo, RiemannConfig cfg, int iters, bool graphs,
-                   int settle_steps = -1, bool diagnose = false) {
+                   int settle_steps = -1, bool diagnose = false,
+                   const TimelineRequest& timeline = {}) {
   BenchRow row;
   row.n = static_cast<double>(cfg.n);
   row.gpus = topo.world;
@@ -87,6 +141,16 @@ BenchRow bench_one(const cli::Topology& topo, RiemannConfig cfg, int iters, bool
     // (RiemannPlan::diagnose_batch; every rank runs it, it has barriers of its own)
     BatchDiag d;
     if (diagnose) d = plan.diagnose_batch(std::min(iters, plan.config().slots));
+    // untimed, last: one batch of the same length from the timeline build of the persistent
+    // launch (RiemannPlan::timeline_batch). Collective like the diagnostic batch, so every
+    // rank runs it; global rank 0's timeline is the one written (one writer, also when every
+    // rank is a process of its own)
+    if (!timeline.file.empty()) {
+      const BatchTimeline tl = plan.timeline_batch(std::min(iters, plan.config().slots));
+      if (rank == 0)
+        write_timeline(timeline.file, tl, cfg, timeline.integrand, timeline.dtype, timeline.div,
+                       d.steps == tl.steps ? d.device_us : 0.0);
+    }
     std::lock_guard<std::mutex> g(mu);
     if (ms > row.ms) row.ms = ms;
     if (rank == topo.rank0) {
@@ -98,6 +162,7 @@ BenchRow bench_one(const cli::Topology& topo, RiemannConfig cfg, int iters, bool
       row.close_in_launch = plan.close_in_launch();
       row.allreduce_to_host = plan.allreduce_to_host();
       row.diag = d;
+      row.timeline_file = timeline.file;
     }
   });
   return row;
@@ -129,6 +194,7 @@ void print_row(const cli::Args& a, const BenchRow& r, const char* integ, const c
         .add("diag_device_us", r.diag.device_us)
         .add("diag_marker_us", r.diag.marker_us)
         .add("diag_host_us", r.diag.wall_us - r.diag.device_us);
+  if (!r.timeline_file.empty()) rec.add("timeline_file", r.timeline_file);
   cli::emit(a, rec, true);
 }
 
@@ -257,7 +323,10 @@ constexpr const char* kUsage =
     "                   [--iters 200] [--gpus G] [--div series_exact|series|ieee] [--unfused] [--no-graph]\n"
     "                   [--block B] [--grid G] [--step-streams S] [--trig-library] [--settle N]\n"
     "                   [--no-multistep] [--slots K] [--close auto|kernel|launch] [--no-ar-host]\n"
-    "                   [--diagnose]\n"
+    "                   [--diagnose] [--slice R/W] [--timeline FILE]\n"
+    "                   (--timeline: after the timed run, one batch from the timeline build of\n"
+    "                   the multi-step launch, per-workgroup device-clock stamps as JSON in FILE;\n"
+    "                   read it with tools/timeline_report.py. --slice: rank R's share of W)\n"
     "       miint sweep [--gpus G]\n"
     "       miint table2d [--grid 4096] [--gpus G] [--slice R/W] [--no-graph]\n"
     "                     [--step-streams S] [--min-wg W] [--settle-ms MS] [--no-multistep]\n"
@@ -284,6 +353,10 @@ int main(int argc, char** argv) {
       return 0;
     }
     if (cmd == "selfcheck") return selfcheck();
+    {  // a malformed --slice is an argument error: said before any device is looked for
+      int r = 0, w = 0;
+      cli::parse_slice(a, &r, &w);
+    }
     const cli::Topology topo = cli::topology(a);
     const int iters = static_cast<int>(a.integer("iters", 100));
     const bool graphs = !a.flag("no-graph");
@@ -301,6 +374,15 @@ int main(int argc, char** argv) {
       // into the device buffer and a copy
       c.close = a.str("close", c.close);
       c.allreduce_to_host = !a.flag("no-ar-host");
+      // --slice R/W: rank R's share of a W-GPU run's step, on this GPU
+      cli::parse_slice(a, &c.slice_rank, &c.slice_world);
+      TimelineRequest tl;
+      tl.file = a.str("timeline", "");
+      tl.integrand = a.str("integrand", "pi4");
+      tl.dtype = a.str("dtype", "fp64");
+      tl.div = a.str("div", "series_exact");
+      if (!tl.file.empty() && c.close == "launch")  // before any run: nothing to time first
+        fail(std::string("--timeline: ") + kTimelineNoCloseInLaunch, __FILE__, __LINE__);
       // validation / A-B: kIeee sin and cos by ocml per sample instead of fast_trig.hpp
       if (a.flag("trig-library")) set_trig_library(true);
       MIINT_CHECK(riemann_block_ok(c.block), "--block must be 64, 128, 256, 512 or 1024");
@@ -309,7 +391,7 @@ int main(int argc, char** argv) {
       // runs pass a few, so the trace holds little more than the timed dispatches)
       const BenchRow r = bench_one(topo, c, iters, graphs,
                                    static_cast<int>(a.integer("settle", -1)),
-                                   a.flag("diagnose"));
+                                   a.flag("diagnose"), tl);
       if (topo.rank0 == 0)
         print_row(a, r, a.str("integrand", "pi4").c_str(), a.str("dtype", "fp64").c_str(),
                   a.str("rule", "left").c_str());
@@ -327,13 +409,7 @@ int main(int argc, char** argv) {
       c.phases = static_cast<int>(a.integer("phases", 0));  // multi-step step phases (0 auto)
       c.graph_steps = static_cast<int>(a.integer("graph-steps", 0));  // per replay (0 auto)
       // --slice R/W: time only rank R's rows of a W-GPU split, on this GPU (no collective)
-      const std::string sl = a.str("slice", "");
-      if (!sl.empty()) {
-        const size_t k = sl.find('/');
-        if (k == std::string::npos) fail("--slice wants R/W", __FILE__, __LINE__);
-        c.rank = std::stoi(sl.substr(0, k));
-        c.world = std::stoi(sl.substr(k + 1));
-      }
+      cli::parse_slice(a, &c.rank, &c.world);
       double value = 0.0, timed = 0.0, ms = 0.0;
       bool bucketed = false, chained = false, multistep = false;
       int streams = 1, phases = 0, resident = 0, min_wg = 0, wgs = 0, gsteps = 0;

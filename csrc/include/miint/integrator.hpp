@@ -165,6 +165,24 @@ struct BatchDiag {
   double boundary_us() const { return device_us - compute_us - tail_us(); }
 };
 
+// One multi-step batch run from the timeline build of its persistent launch
+// (RiemannPlan::timeline_batch, launch_riemann_timeline): what every workgroup did when,
+// inside the launch. Ticks of `stamps` are periods of the constant-rate device clock
+// (clock_khz, hipDeviceAttributeWallClockRate), the same counter on every XCD. The
+// instrumented launch's length is not the plain launch's (it also issues stamps, their waits
+// and their stores): its shares are what is read, not its length (tools/timeline_report.py).
+struct BatchTimeline {
+  int steps = 0, grid = 0, block = 0;
+  int clock_khz = 0;
+  std::vector<uint64_t> stamps;        // [grid][steps + 2]: entry, after each block sum, exit
+  std::vector<uint64_t> shader_clock;  // [grid][2]: the shader clock at entry and at exit
+  std::vector<uint32_t> hw;            // [grid][2]: raw XCC_ID and HW_ID register words
+  double device_us = 0.0;              // hipEvents around the instrumented launch + its close
+  std::vector<double> values;          // the step values (host slots 0 .. steps-1)
+};
+constexpr uint64_t kTimelineUnsetStamp = 0;        // a cell no workgroup wrote
+constexpr uint32_t kTimelineUnsetId = 0xffffffffu;
+
 class RiemannPlan {
  public:
   RiemannPlan(const RiemannConfig& cfg, int device, const Comm* comm = nullptr);
@@ -227,6 +245,16 @@ class RiemannPlan {
   // be part of: the events are queue packets of their own. Collective over ranks (a barrier
   // first, and the batch's all-reduce). Results land in host slots 0 .. nsteps-1.
   BatchDiag diagnose_batch(int nsteps);
+  // One batch of `nsteps` (<= slots; 1 allowed) steps from the timeline build of the
+  // persistent launch, enqueued directly between two hipEvents (BatchTimeline); never part of
+  // a timed region. The plan's own shape, parameters and multi-step partials; the same values
+  // as any batch, in host slots 0 .. nsteps-1. Collective over ranks like diagnose_batch.
+  // Refuses (Error) a plan that is not a multi-step plan, one that closes in the launch, and
+  // one whose grid exceeds the timeline kernel's residency (a second round of workgroups
+  // would make the timeline describe another launch). That residency is the occupancy query's,
+  // which can say more than the device holds at once (7 per CU where 6 entered together,
+  // profiles/r7/timeline.md): tools/timeline_report.py counts the late entries from the stamps.
+  BatchTimeline timeline_batch(int nsteps);
   // Collective: returns once every rank of the plan's communicator has entered (a 1-double
   // all-reduce, drained under the watchdog). No-op without a collective.
   void barrier();
@@ -299,6 +327,9 @@ class RiemannPlan {
   bool ar_host_ok_ = true;            // check_allreduce_to_host's verdict
   bool ar_host_checked_ = false;
   DeviceBuffer<unsigned int> ms_ticket_;  // its arrival counters (close_batch_in_launch)
+  // timeline_batch's buffers (allocated at its first call, sized for `slots` steps)
+  DeviceBuffer<uint64_t> tl_stamps_, tl_shader_;
+  DeviceBuffer<uint32_t> tl_hw_;
   DeviceBuffer<double> result_;
   DeviceBuffer<double> sync_;      // barrier(): the 1-double all-reduce's operand
   DeviceBuffer<unsigned int> ticket_;

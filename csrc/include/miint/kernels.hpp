@@ -144,6 +144,28 @@ void launch_riemann_multistep(const RiemannParams& p, DType dtype, DivMode div,
                               double* partials, int steps, double scale, double* out,
                               hipStream_t stream, unsigned int* ticket = nullptr,
                               bool close_kernel = true);
+// The same launch from its timeline build (riemann.hip riemann_timeline_kernel): thread 0 of
+// every workgroup also records, with `grid` workgroups,
+//   stamps[grid][steps + 2]  the constant-rate device clock (hipDeviceAttributeWallClockRate;
+//                            one counter for every XCD) at kernel entry, after each step's
+//                            block sum (before that step's partial is stored) and at exit;
+//   shader_clock[grid][2]    the workgroup's shader clock at entry and at exit;
+//   hw[grid][2]              the raw XCC_ID and HW_ID register words.
+// Same rotation, same partials, the same closing kernel after it: out[s] is bit for bit the
+// plain launch's. A diagnostic: its stamps and their waits cost time the plain launch does not
+// spend, so its length is not the plain launch's (read shares). The kernel-closed form only
+// (ticket must be null); 1 <= steps <= kMaxMultiSteps (a 1-step launch shows one step's ramp
+// and tail). Residency: riemann_timeline_grid (0 where there is no multi-step kernel).
+constexpr const char* kTimelineNoCloseInLaunch =
+    "the timeline instruments the kernel-closed multi-step launch only (not close = launch)";
+int riemann_timeline_grid(const RiemannParams& p, DType dtype, DivMode div, int block,
+                          int num_cus);
+void launch_riemann_timeline(const RiemannParams& p, DType dtype, DivMode div,
+                             LaunchShape shape, const double* table, int table_n,
+                             double* partials, int steps, double scale, double* out,
+                             hipStream_t stream, uint64_t* stamps, uint64_t* shader_clock,
+                             uint32_t* hw, unsigned int* ticket = nullptr,
+                             bool close_kernel = true);
 // The closing kernel of a multi-step launch on its own (launch_riemann_multistep with
 // close_kernel = false, e.g. to time the two apart): out[s] = scale * step s's sum.
 void launch_multistep_close(const double* partials, int grid, int steps, double scale,

@@ -699,13 +699,104 @@ constexpr int ms_chunk() {
   return __is_same(F, Pi4) ? MIINT_MS_CHUNK : 1;
 }
 
-template <DivMode M, class F, bool CLOSE>
+// ---- the per-workgroup timeline (riemann_timeline_kernel: a diagnostic build of the step
+// loop; in the kernels the plans run no stamp executes). Thread 0 of every workgroup records
+//   stamps[wg][0 .. steps+1]  the constant-rate device clock (one counter for the whole
+//                             device, so workgroups on different XCDs compare): kernel entry,
+//                             after every step's block sum, exit;
+//   shader_clock[wg][0 .. 1]  the workgroup's own shader clock at entry and at exit;
+//   hw[wg][0 .. 1]            the raw XCC_ID and HW_ID register words (decoded on the host).
+// Stamp values leave the kernel through these buffers only: nothing else in the kernel reads
+// them, and no partial is computed from one.
+struct TimelineOut {
+  unsigned long long* stamps;
+  unsigned long long* shader_clock;
+  unsigned* hw;
+};
+// The device clock, and the wait for it in the same statement (a scalar-memory read returns
+// out of order with LDS reads; left to the compiler, the wait's place is anyone's guess). The
+// "memory" clobber keeps the compiler from moving a load or store across the stamp.
+__device__ __forceinline__ unsigned long long timeline_realtime() {
+  unsigned long long t;
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+  return t;
+}
+// The same read tied to a block sum: `sum` is an input operand, so the compiler cannot place
+// the read ahead of the instruction that produces the sum, and a wave issues in order: the
+// clock is read after this wave's last instruction of the block sum (its LDS reads waited
+// for, its adds issued). That is all it says. Waves 1.. of the workgroup are past the sum's
+// barrier and may be anywhere in the next step; other workgroups are not ordered at all.
+__device__ __forceinline__ unsigned long long timeline_realtime_after(double sum) {
+  unsigned long long t;
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(sum) : "memory");
+  return t;
+}
+__device__ __forceinline__ unsigned long long timeline_shader_clock() {
+  unsigned long long t;
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+  return t;
+}
+// A workgroup's row of one of the buffers, from a workgroup index taken fresh where it is
+// used (an empty asm: one v_mov inside thread 0's branch): to the compiler nothing of the
+// address is loop-invariant, and no row address is kept in VGPRs across the step loop.
+template <class T>
+__device__ __forceinline__ T* timeline_row(T* base, int row_len) {
+  unsigned wg = blockIdx.x;
+  asm volatile("" : "+v"(wg));
+  return base + static_cast<size_t>(wg) * static_cast<size_t>(row_len);
+}
+// Kernel entry: both clocks, read by every wave into scalar registers and held there. Wave
+// 0's are stored at exit: a store here needs a divergent branch ahead of make_functor, and
+// with one the register allocation of everything after it came out 13 VGPRs higher in every
+// instantiation (a wave per SIMD less than the plain kernel in most).
+struct TimelineEntry {
+  unsigned long long t, clk;
+};
+__device__ __forceinline__ TimelineEntry timeline_entry() {
+  TimelineEntry e;
+  e.t = timeline_realtime();
+  e.clk = timeline_shader_clock();
+  return e;
+}
+__device__ __forceinline__ void timeline_step(const TimelineOut& tl, int steps, int s,
+                                              double sum) {
+  const unsigned long long t = timeline_realtime_after(sum);
+  timeline_row(tl.stamps, steps + 2)[s + 1] = t;
+}
+// Exit (thread 0): the exit stamps, the entry stamps, and the placement words (a workgroup
+// stays where it was dispatched, so reading them here is reading them at entry).
+__device__ __forceinline__ void timeline_exit(const TimelineOut& tl, int steps,
+                                              const TimelineEntry& e) {
+  const unsigned long long t = timeline_realtime();
+  unsigned long long* clk = timeline_row(tl.shader_clock, 2);
+  clk[0] = e.clk;
+  clk[1] = timeline_shader_clock();
+  unsigned long long* st = timeline_row(tl.stamps, steps + 2);
+  st[0] = e.t;
+  st[steps + 1] = t;
+  unsigned xcc, hw;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  unsigned* id = timeline_row(tl.hw, 2);
+  id[0] = xcc;
+  id[1] = hw;
+}
+
+// TL: the timeline build (riemann_timeline_kernel). Every stamp sits behind `if constexpr
+// (TL)`: with TL = false the body is the code it was without the parameter.
+template <DivMode M, class F, bool CLOSE, bool TL = false>
 __device__ __forceinline__ void multistep_body(const RiemannParams& p, const double* table,
                                                int table_n, double* partials, int steps,
                                                unsigned rot, unsigned* ticket, double scale,
-                                               double* out) {
+                                               double* out, TimelineOut tl = {}) {
   using Acc = typename AccOf<F>::type;
   constexpr int C = ms_chunk<F>();
+  if constexpr (TL) {
+    static_assert(!CLOSE, "the timeline covers the kernel-closed step loop only");
+    static_assert(C == 1, "the timeline covers one step per block sum (MIINT_MS_CHUNK = 1)");
+  }
+  TimelineEntry te{};
+  if constexpr (TL) te = timeline_entry();  // before make_functor: the kernel's first work
   // The block sum's LDS slots alternate between block sums: sum k + 2 writes red[k & 1] only
   // after every wave passed sum k + 1's barrier, which wave 0 reaches after its sum-k reads
   // — so no second barrier per sum, and waves 1-3 start the next step while wave 0 finishes
@@ -758,6 +849,8 @@ __device__ __forceinline__ void multistep_body(const RiemannParams& p, const dou
     if constexpr (__is_same(Acc, double)) v = block_sum_dyn(lane_sum<M>(q, f, vb, sp), red[seq & 1]);
     else v = static_cast<double>(block_sum_dyn(lane_sum<M>(q, f, vb, sp), red_acc[seq & 1]));
     if (threadIdx.x == 0) {
+      if constexpr (TL) timeline_step(tl, steps, s, v);  // after the block sum, before the
+                                                         // partial's store
       // in-launch close: write-through, read by other workgroups' closers in this launch
       if constexpr (CLOSE) slot_store(&partials[static_cast<size_t>(s) * nb + vb], v);
       else partials[static_cast<size_t>(s) * nb + vb] = v;
@@ -765,11 +858,30 @@ __device__ __forceinline__ void multistep_body(const RiemannParams& p, const dou
     vb += rot;
     if (vb >= nb) vb -= nb;
   }
+  if constexpr (TL) {
+    if (threadIdx.x == 0) timeline_exit(tl, steps, te);  // the last partial's store is issued
+  }
   if constexpr (CLOSE) {
     __shared__ int role;
     __syncthreads();  // red[] is the close's block-sum scratch: every wave past its last read
     close_batch_in_launch(partials, nb, steps, ticket, scale, out, red[0], &role);
   }
+}
+// The timeline build of the step loop (see TimelineOut). Names apart from the plans'
+// kernels': the ISA guard follows those by name.
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) void riemann_timeline_kernel(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps,
+    unsigned rot, TimelineOut tl) {
+  multistep_body<M, F, false, true>(p, table, table_n, partials, steps, rot, nullptr, 0.0,
+                                    nullptr, tl);
+}
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) kFullOccupancy void riemann_timeline_kernel_o8(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps,
+    unsigned rot, TimelineOut tl) {
+  multistep_body<M, F, false, true>(p, table, table_n, partials, steps, rot, nullptr, 0.0,
+                                    nullptr, tl);
 }
 template <DivMode M, class F, bool CLOSE>
 __global__ __launch_bounds__(kMaxBlock) void riemann_multistep_kernel(
@@ -972,6 +1084,35 @@ void multistep_per_cu_t(int block, bool close, int* out) {
     *out = close ? multistep_occupancy<M, F, true>(block) : multistep_occupancy<M, F, false>(block);
 }
 
+// The timeline build of the kernel-closed multi-step launch (every instantiation
+// multistep_pays covers), and its residency.
+template <DivMode M, class F>
+void launch_timeline_t(const RiemannParams& p, LaunchShape shape, const double* table,
+                       int table_n, double* partials, int steps, unsigned rot, TimelineOut tl,
+                       hipStream_t stream) {
+  if constexpr (!multistep_pays<M, F>())
+    fail("this integrand/division keeps chained batches (no multi-step kernel, no timeline)",
+         __FILE__, __LINE__);
+  else if constexpr (multistep_o8<M, F>())
+    riemann_timeline_kernel_o8<M, F><<<shape.grid, shape.block, 0, stream>>>(
+        p, table, table_n, partials, steps, rot, tl);
+  else
+    riemann_timeline_kernel<M, F><<<shape.grid, shape.block, 0, stream>>>(
+        p, table, table_n, partials, steps, rot, tl);
+}
+template <DivMode M, class F>
+void timeline_per_cu_t(int block, int* out) {
+  *out = 0;
+  if constexpr (multistep_pays<M, F>()) {
+    if constexpr (multistep_o8<M, F>())
+      MIINT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          out, reinterpret_cast<const void*>(&riemann_timeline_kernel_o8<M, F>), block, 0));
+    else
+      MIINT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          out, reinterpret_cast<const void*>(&riemann_timeline_kernel<M, F>), block, 0));
+  }
+}
+
 // kIeee Pi4 launches take Pi4::recip_narrow when both end coordinates (the extremes: x is
 // linear in the sample index) stay below kPi4NarrowMaxX in magnitude; NaN ends do not.
 std::atomic<bool> g_pi4_library_division{false};  // validation switch: always Pi4Wide
@@ -1080,6 +1221,12 @@ template <DivMode M, class F> struct MultiStepOp {
 };
 template <DivMode M, class F> struct MultiStepOccOp {
   static void run(int block, bool close, int* out) { multistep_per_cu_t<M, F>(block, close, out); }
+};
+template <DivMode M, class F> struct TimelineOp {
+  template <class... A> static void run(A... a) { launch_timeline_t<M, F>(a...); }
+};
+template <DivMode M, class F> struct TimelineOccOp {
+  static void run(int block, int* out) { timeline_per_cu_t<M, F>(block, out); }
 };
 template <DivMode M, class F> struct TileLenOp {
   static void run(int* out) { *out = F::template tile_len<M>(); }
@@ -1226,6 +1373,18 @@ int riemann_multistep_grid(const RiemannParams& p, DType dtype, DivMode div, int
   return per_cu * num_cus;  // 0: this instantiation runs chained batches
 }
 
+// rotation: the blocks owning one tile round more than the rest (lane_sum: the first
+// `heavy`) move by `heavy` blocks a step, so each workgroup gets its share of them
+static unsigned multistep_rot(const RiemannParams& p, DType dtype, DivMode eff,
+                              LaunchShape shape) {
+  int tl = 0;
+  dispatch<TileLenOp>(p, dtype, eff, &tl);
+  const uint64_t lanes = static_cast<uint64_t>(shape.grid) * static_cast<uint64_t>(shape.block);
+  const uint64_t extra = (p.n / static_cast<uint64_t>(tl)) % lanes;
+  const unsigned heavy = static_cast<unsigned>((extra + shape.block - 1) / shape.block);
+  return heavy % static_cast<unsigned>(shape.grid);
+}
+
 void launch_riemann_multistep(const RiemannParams& p, DType dtype, DivMode div,
                               LaunchShape shape, const double* table, int table_n,
                               double* partials, int steps, double scale, double* out,
@@ -1235,18 +1394,43 @@ void launch_riemann_multistep(const RiemannParams& p, DType dtype, DivMode div,
   MIINT_CHECK(steps >= 1 && steps <= kMaxMultiSteps, "multi-step launch: 1..64 steps");
   MIINT_CHECK(partials != nullptr && out != nullptr, "multi-step launch needs partials and results");
   const DivMode eff = effective_div(p, div, dtype);
-  // rotation: the blocks owning one tile round more than the rest (lane_sum: the first
-  // `heavy`) move by `heavy` blocks a step, so each workgroup gets its share of them
-  int tl = 0;
-  dispatch<TileLenOp>(p, dtype, eff, &tl);
-  const uint64_t lanes = static_cast<uint64_t>(shape.grid) * static_cast<uint64_t>(shape.block);
-  const uint64_t extra = (p.n / static_cast<uint64_t>(tl)) % lanes;
-  const unsigned heavy = static_cast<unsigned>((extra + shape.block - 1) / shape.block);
-  const unsigned rot = heavy % static_cast<unsigned>(shape.grid);
+  const unsigned rot = multistep_rot(p, dtype, eff, shape);
   dispatch<MultiStepOp>(p, dtype, eff, prepared(p, eff), shape, table, table_n, partials, steps,
                         rot, ticket, scale, out, stream);
   MIINT_HIP(hipGetLastError());
   if (ticket || !close_kernel) return;  // closed inside the launch, or by the caller
+  launch_multistep_close(partials, shape.grid, steps, scale, out, shape.block, stream);
+}
+
+int riemann_timeline_grid(const RiemannParams& p, DType dtype, DivMode div, int block,
+                          int num_cus) {
+  MIINT_CHECK(riemann_block_ok(block), "unsupported Riemann block size");
+  int per_cu = 0;
+  dispatch<TimelineOccOp>(p, dtype, effective_div(p, div, dtype), block, &per_cu);
+  return per_cu * num_cus;  // 0: this instantiation runs chained batches
+}
+
+void launch_riemann_timeline(const RiemannParams& p, DType dtype, DivMode div,
+                             LaunchShape shape, const double* table, int table_n,
+                             double* partials, int steps, double scale, double* out,
+                             hipStream_t stream, uint64_t* stamps, uint64_t* shader_clock,
+                             uint32_t* hw, unsigned int* ticket, bool close_kernel) {
+  check_shape(shape);
+  check_params(p, table, table_n);
+  MIINT_CHECK(ticket == nullptr, kTimelineNoCloseInLaunch);
+  MIINT_CHECK(steps >= 1 && steps <= kMaxMultiSteps, "timeline launch: 1..64 steps");
+  MIINT_CHECK(partials != nullptr && out != nullptr, "timeline launch needs partials and results");
+  MIINT_CHECK(stamps != nullptr && shader_clock != nullptr && hw != nullptr,
+              "timeline launch needs its three buffers");
+  const DivMode eff = effective_div(p, div, dtype);
+  const unsigned rot = multistep_rot(p, dtype, eff, shape);  // the plain launch's rotation
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stamp words are 64-bit");
+  const TimelineOut tl{reinterpret_cast<unsigned long long*>(stamps),
+                       reinterpret_cast<unsigned long long*>(shader_clock), hw};
+  dispatch<TimelineOp>(p, dtype, eff, prepared(p, eff), shape, table, table_n, partials, steps,
+                       rot, tl, stream);
+  MIINT_HIP(hipGetLastError());
+  if (!close_kernel) return;
   launch_multistep_close(partials, shape.grid, steps, scale, out, shape.block, stream);
 }
 

@@ -3,12 +3,15 @@
 // Device memory crosses the boundary as integer addresses (torch.Tensor.data_ptr()) and
 // streams as integer handles (torch.cuda.Stream.cuda_stream), so the module has no libtorch
 // ABI dependency and no hipify step; it links only libamdhip64 and librccl.
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "miint/comm.hpp"
 #include "miint/expr.hpp"
@@ -331,6 +334,32 @@ PYBIND11_MODULE(_miint, m) {
              r["device_us"] = d.device_us;
              r["staged_us"] = d.staged_us;
              r["wall_us"] = d.wall_us;
+             return r;
+           }, py::arg("steps"))
+      .def("timeline_batch", [](RiemannPlan& p, int steps) {
+             BatchTimeline t;
+             {
+               py::gil_scoped_release nogil;
+               t = p.timeline_batch(steps);
+             }
+             // numpy arrays (copies): stamps [grid, steps + 2], shader_clock and hw [grid, 2]
+             auto arr64 = [](const std::vector<uint64_t>& v, py::ssize_t rows, py::ssize_t cols) {
+               py::array_t<uint64_t> a({rows, cols});
+               std::copy(v.begin(), v.end(), a.mutable_data());
+               return a;
+             };
+             py::array_t<uint32_t> hw({static_cast<py::ssize_t>(t.grid), py::ssize_t(2)});
+             std::copy(t.hw.begin(), t.hw.end(), hw.mutable_data());
+             py::dict r;
+             r["steps"] = t.steps;
+             r["grid"] = t.grid;
+             r["block"] = t.block;
+             r["clock_khz"] = t.clock_khz;
+             r["device_us"] = t.device_us;
+             r["stamps"] = arr64(t.stamps, t.grid, t.steps + 2);
+             r["shader_clock"] = arr64(t.shader_clock, t.grid, 2);
+             r["hw"] = hw;
+             r["values"] = t.values;
              return r;
            }, py::arg("steps"))
       .def("host_result", &RiemannPlan::host_result)

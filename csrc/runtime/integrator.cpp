@@ -587,6 +587,70 @@ BatchDiag RiemannPlan::diagnose_batch(int nsteps) {
   return d;
 }
 
+BatchTimeline RiemannPlan::timeline_batch(int nsteps) {
+  MIINT_CHECK(nsteps >= 1 && nsteps <= cfg_.slots, "timeline_batch: 1 <= steps <= slots");
+  MIINT_CHECK(multistep(), "timeline_batch: not a multi-step plan (its batches run chained or "
+                           "fused launches: there is no persistent launch to time)");
+  MIINT_CHECK(!close_launch_, std::string("timeline_batch: ") + kTimelineNoCloseInLaunch);
+  DeviceGuard g(device_);
+  TraceRange tr("miint.plan.timeline_batch");
+  const DeviceInfo info = device_info(device_);
+  const int resident =
+      riemann_timeline_grid(params_, cfg_.dtype, cfg_.div, shape_.block, info.num_cus);
+  MIINT_CHECK(shape_.grid <= resident,
+              "timeline_batch: the timeline kernel holds " + std::to_string(resident) +
+                  " workgroups of " + std::to_string(shape_.block) + " threads at once, the plan "
+                  "launches " + std::to_string(shape_.grid) + " (a second round of workgroups "
+                  "would be another launch's timeline)");
+  BatchTimeline t;
+  t.steps = nsteps;
+  t.grid = shape_.grid;
+  t.block = shape_.block;
+  MIINT_HIP(hipDeviceGetAttribute(&t.clock_khz, hipDeviceAttributeWallClockRate, device_));
+  MIINT_CHECK(t.clock_khz > 0, "timeline_batch: the device reports no wall clock rate");
+  const size_t grid = static_cast<size_t>(shape_.grid);
+  if (tl_stamps_.size() == 0) {
+    tl_stamps_ = DeviceBuffer<uint64_t>(grid * static_cast<size_t>(cfg_.slots + 2));
+    tl_shader_ = DeviceBuffer<uint64_t>(grid * 2);
+    tl_hw_ = DeviceBuffer<uint32_t>(grid * 2);
+  }
+  check_allreduce_to_host();
+  hipStream_t cs = compute_.get();
+  const size_t nstamp = grid * static_cast<size_t>(nsteps + 2);
+  sync();
+  barrier();
+  // sentinels: a cell no workgroup wrote stays kTimelineUnsetStamp / kTimelineUnsetId
+  MIINT_HIP(hipMemsetAsync(tl_stamps_.get(), 0, tl_stamps_.bytes(), cs));
+  MIINT_HIP(hipMemsetAsync(tl_shader_.get(), 0, tl_shader_.bytes(), cs));
+  MIINT_HIP(hipMemsetAsync(tl_hw_.get(), 0xff, tl_hw_.bytes(), cs));
+  Event a0, a1;
+  a0.record(cs);
+  launch_riemann_timeline(params_, cfg_.dtype, cfg_.div, shape_, table_.get(),
+                          static_cast<int>(cfg_.table.size()), ms_partials_.get(), nsteps, scale_,
+                          result_ptr(0), cs, tl_stamps_.get(), tl_shader_.get(), tl_hw_.get());
+  a1.record(cs);
+  // the step values go where any batch's go (enqueue_batch)
+  if (bucketed())
+    enqueue_bucket_reduce(cs, nsteps);
+  else if (!direct_)
+    MIINT_HIP(hipMemcpyAsync(host_.get(), result_.get(), sizeof(double) * nsteps,
+                             hipMemcpyDeviceToHost, cs));
+  t.stamps.resize(nstamp);
+  t.shader_clock.resize(grid * 2);
+  t.hw.resize(grid * 2);
+  MIINT_HIP(hipMemcpyAsync(t.stamps.data(), tl_stamps_.get(), nstamp * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, cs));
+  MIINT_HIP(hipMemcpyAsync(t.shader_clock.data(), tl_shader_.get(), tl_shader_.bytes(),
+                           hipMemcpyDeviceToHost, cs));
+  MIINT_HIP(hipMemcpyAsync(t.hw.data(), tl_hw_.get(), tl_hw_.bytes(), hipMemcpyDeviceToHost, cs));
+  sync();
+  last_mode_ = 1;
+  t.device_us = Event::elapsed_ms(a0, a1) * 1e3;
+  t.values.resize(static_cast<size_t>(nsteps));
+  for (int j = 0; j < nsteps; ++j) t.values[static_cast<size_t>(j)] = host_[j];
+  return t;
+}
+
 OneShotTiming RiemannPlan::time_one_shot(int reps, const std::string& mode, int warmup) {
   MIINT_CHECK(reps >= 1 && warmup >= 0, "time_one_shot: reps >= 1");
   MIINT_CHECK(!collective(), "time_one_shot: single-rank plans only");

@@ -215,6 +215,19 @@ class Integrator:
         if self._plan is not None:
             self._plan.sync()
 
+    def timeline(self, steps: int) -> dict:
+        """One multi-step batch from the timeline build of its persistent launch
+        (``RiemannPlan::timeline_batch``): per workgroup, device-clock stamps at kernel entry,
+        after every step's block sum and at exit (``stamps`` uint64 [grid, steps + 2], ticks of
+        ``clock_khz``), the shader clock at entry and exit, and the raw XCC_ID / HW_ID words
+        (``hw``); ``xcc`` is the XCC id decoded from them. A diagnostic, never timed: read its
+        shares (``tools/timeline_report.py``), not its length."""
+        if self._plan is None:
+            raise RuntimeError("timeline needs backend='hip'")
+        t = self._plan.timeline_batch(steps)
+        t["xcc"] = t["hw"][:, 0] & 0xF
+        return t
+
 
 def integrate(integrand: str = "pi4", n: int = 10**9, **kw) -> IntegrationResult:
     return Integrator(integrand, n=n, **kw).run()
