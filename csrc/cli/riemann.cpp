@@ -24,7 +24,10 @@
 // --expr "EXPR" integrates any f(x) given as one C++ expression over x (HIP device math:
 // sin, exp, pow, ...), compiled at run time for gfx950 with hipRTC (miint/expr.hpp) — where
 // the reference edits riemann.cpp:37 and recompiles; with --device cpu, compiled for the
-// host cores instead (HostExpr). --analytic V adds the error vs V.
+// host cores instead (HostExpr). --analytic V adds the error vs V. With --params FILE (one
+// row of numbers per line) or --linspace p0=LO:HI:COUNT the expression may also mention
+// p0..p7 and every row is integrated in one launch (ExprSweep): one line per row (index,
+// parameters, value), or with --json one record carrying rows, nparams and values.
 //
 //   ./riemann [--n 1e9] [--gpus G] [--integrand sin|pi4|poly|train] [--rule left|mid|right]
 //             [--dtype fp64|fp32|fp32acc] [--iters K] [--block 64..1024] [--grid G] [--parity]
@@ -156,8 +159,130 @@ int run_host_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int i
   return 0;
 }
 
+// --expr with --params FILE or --linspace p0=LO:HI:COUNT: a parameter sweep, f(x, p0..p7)
+// for every row in one launch (ExprSweep; --device cpu: HostExprSweep). Ranks slice the
+// samples, not the rows, and the rows' values meet in one all-reduce.
+struct SweepRows {
+  std::vector<double> params;  // rows x nparams
+  int nparams = 0;
+  uint64_t rows = 0;
+};
+
+SweepRows sweep_rows(const cli::Args& a) {
+  MIINT_CHECK(!(a.has("params") && a.has("linspace")), "give --params FILE or --linspace, not both");
+  SweepRows s;
+  if (a.has("params")) {
+    s.params = load_param_rows(a.str("params", ""), &s.nparams);
+  } else {
+    s.params = linspace_param_rows(a.str("linspace", ""));
+    s.nparams = 1;
+  }
+  s.rows = s.params.size() / s.nparams;
+  return s;
+}
+
+void print_sweep(const cli::Args& a, const SweepRows& s, const std::vector<double>& values) {
+  if (a.flag("json")) return;  // the record carries the values
+  for (uint64_t k = 0; k < s.rows; ++k) {
+    std::printf("%llu", static_cast<unsigned long long>(k));
+    for (int j = 0; j < s.nparams; ++j) std::printf(" %.17g", s.params[k * s.nparams + j]);
+    std::printf(" %.13g\n", values[k]);
+  }
+}
+
+cli::JsonRecord& add_sweep(cli::JsonRecord& r, const SweepRows& s,
+                           const std::vector<double>& values) {
+  std::string vs = "[";
+  for (size_t k = 0; k < values.size(); ++k) {
+    char b[40];
+    if (std::isfinite(values[k])) std::snprintf(b, sizeof b, "%s%.17g", k ? "," : "", values[k]);
+    else std::snprintf(b, sizeof b, "%snull", k ? "," : "");
+    vs += b;
+  }
+  return r.add("rows", static_cast<int>(s.rows)).add("nparams", s.nparams)
+      .add_raw("values", vs + "]");
+}
+
+int run_host_expr_sweep(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  const std::string expr = a.str("expr", "");
+  const SweepRows sw = sweep_rows(a);
+  cli::HostRanks hr = cli::host_ranks(a);
+  HostPool pool(hr.threads);
+  const HostExprSweep he(expr, sw.nparams);
+  uint64_t b = 0, c = 0;
+  rank_slice(cfg.n, hr.rank, hr.world, &b, &c);
+  std::vector<double> values;
+  double host_ms = 0.0;
+  for (int i = 0; i < iters; ++i) {  // best of --iters
+    if (hr.comm) hr.comm->barrier();
+    const double t0 = wall_seconds();
+    std::vector<double> v =
+        he.integrate(sw.params, sw.rows, cfg.a, cfg.b, cfg.n, cfg.rule, b, c, pool);
+    if (hr.comm) hr.comm->allreduce_sum(v.data(), v.size());
+    const double ms = (wall_seconds() - t0) * 1e3;
+    if (i == 0 || ms < host_ms) host_ms = ms;
+    values = v;
+  }
+  if (hr.rank != 0) return 0;
+  const double secs = wall_seconds() - process_start_seconds();
+  print_sweep(a, sw, values);
+  cli::JsonRecord r;
+  r.add("program", "riemann").add("device", "cpu").add("expr", expr).add("a", cfg.a)
+      .add("b", cfg.b).add("n", nd).add("rule", a.str("rule", "left")).add("ranks", hr.world)
+      .add("threads_per_rank", pool.threads());
+  add_sweep(r, sw, values);
+  cli::emit(a, r.add("host_ms", host_ms).add("ms_per_sweep", host_ms)
+                   .add("subintervals_per_s",
+                        host_ms > 0 ? static_cast<double>(sw.rows) * nd / (host_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
+int run_expr_sweep(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (cli::on_cpu(a)) return run_host_expr_sweep(a, cfg, nd, iters);
+  const std::string expr = a.str("expr", "");
+  const SweepRows sw = sweep_rows(a);
+  const cli::Topology topo = cli::topology(a);
+  std::vector<double> values;
+  double dev_ms = 0.0;
+  std::mutex mu;
+  cli::RankFacts facts;
+  cli::run_ranks(topo, [&](int rank, int dev, const Comm* comm) {
+    ExprSweep es(expr, sw.nparams, dev, cfg.grid);
+    RankAgree agree(comm);
+    uint64_t b = 0, c = 0;
+    rank_slice(cfg.n, rank, topo.world, &b, &c);
+    const std::vector<double> v =
+        es.integrate(sw.params, sw.rows, cfg.a, cfg.b, cfg.n, cfg.rule, b, c, 1.0, comm);
+    // barrier right before the clock starts; the slowest rank's time
+    const double ms = agree.max(es.time(sw.params, sw.rows, cfg.a, cfg.b, cfg.n, cfg.rule, b, c,
+                                        iters, [&] { agree.barrier(); },
+                                        [&] { fault::delay(rank); }));
+    std::lock_guard<std::mutex> g(mu);
+    if (rank == topo.rank0) {
+      values = v;
+      dev_ms = ms;
+      facts.note(comm);
+    }
+  });
+  if (topo.rank0 != 0) return 0;
+  const double secs = wall_seconds() - process_start_seconds();
+  print_sweep(a, sw, values);
+  cli::JsonRecord r;
+  r.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b).add("n", nd)
+      .add("rule", a.str("rule", "left")).add("gpus", topo.world);
+  add_sweep(r, sw, values);
+  facts.add(r, topo);
+  cli::emit(a, r.add("device_ms", dev_ms).add("ms_per_sweep", dev_ms)
+                   .add("subintervals_per_s",
+                        dev_ms > 0 ? static_cast<double>(sw.rows) * nd / (dev_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (a.has("params") || a.has("linspace")) return run_expr_sweep(a, cfg, nd, iters);
   if (cli::on_cpu(a)) return run_host_expr(a, cfg, nd, iters);
   const std::string expr = a.str("expr", "");
   const cli::Topology topo = cli::topology(a);
@@ -213,6 +338,7 @@ constexpr const char* kUsage =
     "               [--json] [--jsonl FILE] [--profile FILE]\n"
     "               [--device cpu [--threads T] [--ranks P]]\n"
     "               [--expr EXPR --a A --b B [--analytic V]]\n"
+    "               [--expr EXPR --params FILE | --linspace p0=LO:HI:COUNT]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
     "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n";
 
@@ -256,6 +382,8 @@ int main(int argc, char** argv) {
     if (f == Integrand::kTable) cfg.table = prof;
     if (f == Integrand::kPoly) cfg.coef = {1.0, -0.5, 0.25, 0.125};
 
+    MIINT_CHECK(a.has("expr") || !(a.has("params") || a.has("linspace")),
+                "--params / --linspace sweep the parameters of an --expr integrand");
     if (a.has("expr")) return run_expr(a, cfg, nd, iters);
     if (cli::on_cpu(a)) return run_host(a, cfg, nd, iters);
     const cli::Topology topo = cli::topology(a);

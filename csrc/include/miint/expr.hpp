@@ -25,6 +25,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "miint/comm.hpp"
 #include "miint/common.hpp"
@@ -40,6 +41,10 @@ std::string expr_source(const std::string& expr);
 // Compile `expr` for gfx950 with hipRTC (no device needed); returns the code object. Throws
 // with the compiler log on failure.
 std::string expr_compile(const std::string& expr);
+namespace detail {
+// hipRTC compile of `src` for gfx950 (-O3); `expr` names the expression in the error.
+std::string rtc_compile(const std::string& src, const std::string& expr);
+}  // namespace detail
 
 class ExprIntegrator {
  public:
@@ -70,6 +75,95 @@ class ExprIntegrator {
   Stream stream_;
   DeviceBuffer<double> partials_, out_;
   PinnedBuffer<double> host_;
+  Event e0_, e1_;
+};
+
+// ---------------------------------------------------------------------------------------
+// Parameter sweeps: f(x, p0, ..., p{nparams-1}) over K parameter rows in one launch.
+//
+// A family of integrals (exp(-p0*x*x) over 1000 widths) through ExprIntegrator costs a
+// compile, a module load, two launches and a sync per value. Here the expression may also
+// mention p0..p7; the rows' values are kernel data (params[k*nparams + j]), so one compile
+// and one pair of launches serve every row:
+//
+//   miint_expr_sweep_partials  grid (gx, gy): gx sample slices x gy row lanes. Workgroup
+//                              (bx, by) walks rows by, by + gy, ...; per row it runs the
+//                              per-sample loop of miint_expr_partials over its bx share of
+//                              the samples and writes one partial per (row, bx).
+//   miint_expr_sweep_close     one workgroup per row sums the row's gx partials in index
+//                              order -> out[k] = scale * sum
+//
+// Rows are independent and the close is its own kernel: no workgroup waits on another, so
+// nothing depends on co-residency. gx depends on the sample count (and an explicit grid)
+// only, never on the row count, so a row's value is bitwise the same alone, in any batch
+// and at any position.
+// ---------------------------------------------------------------------------------------
+constexpr int kSweepMaxParams = 8;
+constexpr uint64_t kSweepMaxRows = 1ull << 20;
+constexpr int kSweepMaxGrid = 2048;  // gx, and about gx * gy
+// Least samples per lane worth one more workgroup along x. Measured over {16, 64, 256, 1024}
+// (profiles/r8/expr_sweep.md): below 256 the per-row reduction shows (many small rows are
+// 3 % slower at 64, 14 % at 16), at 1024 a few middling rows leave most of the device idle.
+constexpr uint64_t kSweepMinSamplesPerLane = 256;
+
+// Kernel source for f(x, p0..p{nparams-1}); a pJ at or above nparams fails in the compiler.
+std::string expr_sweep_source(const std::string& expr, int nparams);
+// hipRTC compile for gfx950 (no device needed), cached per (expression, nparams).
+std::string expr_sweep_compile(const std::string& expr, int nparams);
+
+struct SweepShape {
+  int gx = 1, gy = 1;
+};
+// Launch shape of a sweep of `rows` rows over n_local samples each (no device needed):
+// gx = grid if given, else clamp(ceil(n_local / (256 * kSweepMinSamplesPerLane)), 1, 2048);
+// gy = clamp(2048 / gx, 1, rows). Throws when a lane's share of n_local would not fit the
+// kernel's 32-bit per-lane count.
+SweepShape expr_sweep_shape(uint64_t n_local, uint64_t rows, int grid = 0);
+
+// Parameter rows from a text file: one row per line, numbers separated by commas, semicolons
+// or whitespace, # starts a comment (the --profile reader's rules). Every row has the same
+// width (<= 8), returned in *nparams; row-major values. Errors name the file, line and row.
+std::vector<double> load_param_rows(const std::string& path, int* nparams);
+// "p0=LO:HI:COUNT": COUNT evenly spaced one-parameter rows from LO to HI inclusive.
+std::vector<double> linspace_param_rows(const std::string& spec);
+
+class ExprSweep {
+ public:
+  ExprSweep(const std::string& expr, int nparams, int device = 0, int grid = 0);
+  ~ExprSweep();
+  ExprSweep(const ExprSweep&) = delete;
+  ExprSweep& operator=(const ExprSweep&) = delete;
+  // out[k] = h * scale * sum f(a + (i + off) h, params[k*nparams ..]) over samples
+  // [begin, begin + count) of the n-sample rule on [a, b], for `rows` rows (params is
+  // rows x nparams, row-major; rows is explicit because nparams may be 0). One upload of
+  // the rows, one partials and one close launch (more only when rows * gx partials would
+  // pass 2^24 doubles: then rows go in chunks), one all-reduce of the rows' values when
+  // the communicator has more than one rank, one copy back, one sync.
+  std::vector<double> integrate(const std::vector<double>& params, uint64_t rows, double a,
+                                double b, uint64_t n, Rule rule, uint64_t begin, uint64_t count,
+                                double scale = 1.0, const Comm* comm = nullptr);
+  // Device ms per sweep over `iters` back-to-back sweeps (events; the rows are uploaded
+  // once, before the clock). Hooks as in ExprIntegrator::time.
+  double time(const std::vector<double>& params, uint64_t rows, double a, double b, uint64_t n,
+              Rule rule, uint64_t begin, uint64_t count, int iters,
+              const std::function<void()>& at_start = {},
+              const std::function<void()>& at_end = {});
+  const std::string& expression() const { return expr_; }
+  int nparams() const { return nparams_; }
+
+ private:
+  void check(const std::vector<double>& params, uint64_t rows, uint64_t n, uint64_t begin,
+             uint64_t count) const;
+  void upload(const std::vector<double>& params, uint64_t rows, int gx, hipStream_t s);
+  void enqueue(double a, double h, double off, uint64_t begin, uint64_t count, uint64_t rows,
+               SweepShape shape, double scale, hipStream_t s);
+  std::string expr_;
+  int nparams_, device_, grid_;
+  hipModule_t module_ = nullptr;
+  hipFunction_t partials_fn_ = nullptr, close_fn_ = nullptr;
+  Stream stream_;
+  DeviceBuffer<double> params_, partials_, out_;
+  PinnedBuffer<double> host_params_, host_out_;
   Event e0_, e1_;
 };
 

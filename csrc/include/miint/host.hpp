@@ -98,6 +98,27 @@ class HostExpr {
   void* fn_ = nullptr;
 };
 
+// A parameter sweep on the host: f(x, p0..p{nparams-1}) from the same translation-unit
+// generator (the row's values passed to the compiled sum), cached per (expression, nparams).
+// The --device cpu side of ExprSweep (miint/expr.hpp) and its CPU reference.
+class HostExprSweep {
+ public:
+  HostExprSweep(const std::string& expr, int nparams);
+  // One value per row (params: rows x nparams, row-major): h * sum f(a + (i + off) h, row)
+  // over [begin, begin + count). Rows x thread slices: every thread takes its slice of each
+  // row, added per row in thread order, so a row's value is HostExpr's for the same f.
+  std::vector<double> integrate(const std::vector<double>& params, uint64_t rows, double a,
+                                double b, uint64_t n, Rule rule, uint64_t begin, uint64_t count,
+                                HostPool& pool) const;
+  const std::string& expression() const { return expr_; }
+  int nparams() const { return nparams_; }
+
+ private:
+  std::string expr_;
+  int nparams_;
+  void* fn_ = nullptr;
+};
+
 // Host collectives across processes: a TCP star through rank 0 (rank 0 listens on
 // addr:port, every other rank connects once and keeps its socket). Reductions sum in rank
 // order on rank 0, so every rank receives bitwise the same values. Every receive is bounded

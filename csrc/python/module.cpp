@@ -52,6 +52,28 @@ RiemannParams make_params(int integrand, double a, double h, double off, uint64_
   return p;
 }
 
+// Sweep parameters: a list of rows or a 2-D float64 array, K x nparams -> row-major values.
+// An empty sequence is K = 0; ragged or non-numeric rows are refused here.
+using ParamRows = py::object;
+std::vector<double> param_rows(const ParamRows& obj, int nparams, uint64_t* rows) {
+  auto arr = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(obj);
+  if (!arr) {
+    PyErr_Clear();
+    fail("expression sweep: params must be K rows of " + std::to_string(nparams) +
+             " numbers (a list of rows or a 2-D float64 array)", __FILE__, __LINE__);
+  }
+  if (arr.size() == 0 && arr.ndim() >= 1 && arr.shape(0) == 0) {
+    *rows = 0;
+    return {};
+  }
+  MIINT_CHECK(arr.ndim() == 2, "expression sweep: params must be 2-D (K rows x nparams)");
+  MIINT_CHECK(arr.shape(1) == nparams,
+              "expression sweep: rows of " + std::to_string(arr.shape(1)) +
+                  " values, the expression was built for nparams = " + std::to_string(nparams));
+  *rows = static_cast<uint64_t>(arr.shape(0));
+  return std::vector<double>(arr.data(), arr.data() + arr.size());
+}
+
 }  // namespace
 
 static const char* scan_algo_name(ScanAlgo a) {
@@ -667,6 +689,73 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("count"), py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprIntegrator::expression);
 
+  // parameter sweeps: f(x, p0..p7) over K rows per launch
+  m.def("expr_sweep_source", &expr_sweep_source, py::arg("expr"), py::arg("nparams"),
+        "kernel source generated for an expression over x and p0..p{nparams-1}");
+  m.def("expr_sweep_compile", [](const std::string& e, int nparams) {
+          std::string code;
+          {
+            py::gil_scoped_release nogil;
+            code = expr_sweep_compile(e, nparams);
+          }
+          return py::bytes(code);
+        },
+        py::arg("expr"), py::arg("nparams"),
+        "compile a sweep expression for gfx950 with hipRTC (no device needed); the code object");
+  m.def("expr_sweep_shape", [](uint64_t n_local, uint64_t rows, int grid) {
+          const SweepShape s = expr_sweep_shape(n_local, rows, grid);
+          return py::make_tuple(s.gx, s.gy);
+        },
+        py::arg("n_local"), py::arg("rows"), py::arg("grid") = 0,
+        "(gx, gy) of a sweep launch; gx never depends on rows");
+  m.def("load_param_rows", [](const std::string& path) {
+          int np = 0;
+          std::vector<double> v = load_param_rows(path, &np);
+          const py::ssize_t rows = np ? static_cast<py::ssize_t>(v.size()) / np : 0;
+          py::array_t<double> a({rows, static_cast<py::ssize_t>(np)});
+          std::copy(v.begin(), v.end(), a.mutable_data());
+          return a;
+        },
+        py::arg("path"), "parameter rows of a text file as a 2-D float64 array");
+  m.def("linspace_param_rows", [](const std::string& spec) {
+          std::vector<double> v = linspace_param_rows(spec);
+          py::array_t<double> a({static_cast<py::ssize_t>(v.size()), py::ssize_t(1)});
+          std::copy(v.begin(), v.end(), a.mutable_data());
+          return a;
+        },
+        py::arg("spec"), "p0=LO:HI:COUNT as a COUNT x 1 float64 array");
+  py::class_<ExprSweep>(m, "ExprSweep",
+                        "f(x, p0..p7) as an expression: K parameter rows per launch (hipRTC)")
+      .def(py::init<const std::string&, int, int, int>(), py::arg("expr"), py::arg("nparams"),
+           py::arg("device") = 0, py::arg("grid") = 0)
+      .def("integrate",
+           [](ExprSweep& e, const ParamRows& params, double a, double b, uint64_t n, Rule rule,
+              uint64_t begin, uint64_t count, double scale, const Comm* comm) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             std::vector<double> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.integrate(p, rows, a, b, n, rule, begin, count, scale, comm);
+             }
+             return py::array_t<double>(static_cast<py::ssize_t>(v.size()), v.data());
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"), py::arg("n"), py::arg("rule"),
+           py::arg("begin"), py::arg("count"), py::arg("scale") = 1.0,
+           py::arg("comm") = nullptr)
+      .def("time",
+           [](ExprSweep& e, const ParamRows& params, double a, double b, uint64_t n, Rule rule,
+              uint64_t begin, uint64_t count, int iters) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             py::gil_scoped_release nogil;
+             return e.time(p, rows, a, b, n, rule, begin, count, iters);
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"), py::arg("n"), py::arg("rule"),
+           py::arg("begin"), py::arg("count"), py::arg("iters"))
+      .def_property_readonly("expression", &ExprSweep::expression)
+      .def_property_readonly("nparams", &ExprSweep::nparams);
+
   // ------------------------------------------------------------------ host (CPU) engine
   m.def("host_isa", &host_isa, "vector ISA the host kernels dispatch to: avx512|avx2|base");
   py::class_<HostPool>(m, "HostPool", "persistent host worker threads (0 = one per core)")
@@ -683,6 +772,26 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("rule"), py::arg("begin"), py::arg("count"), py::arg("pool"),
            py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &HostExpr::expression);
+  py::class_<HostExprSweep>(m, "HostExprSweep",
+                            "f(x, p0..p7) as an expression, K rows on the host cores")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("nparams"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("integrate",
+           [](const HostExprSweep& e, const ParamRows& params, double a, double b, uint64_t n,
+              Rule rule, uint64_t begin, uint64_t count, HostPool& pool) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             std::vector<double> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.integrate(p, rows, a, b, n, rule, begin, count, pool);
+             }
+             return py::array_t<double>(static_cast<py::ssize_t>(v.size()), v.data());
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"), py::arg("n"), py::arg("rule"),
+           py::arg("begin"), py::arg("count"), py::arg("pool"))
+      .def_property_readonly("expression", &HostExprSweep::expression)
+      .def_property_readonly("nparams", &HostExprSweep::nparams);
   m.def("host_riemann_mpi_parity", &host_riemann_mpi_parity, py::arg("comm_size"), py::arg("n"),
         py::arg("range"), py::arg("pool"), py::call_guard<py::gil_scoped_release>(),
         "the reference's mpirun -np P ./riemann, bit for bit, with its P-1 workers on threads");

@@ -102,13 +102,8 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr_finalize(
 )";
 }
 
-std::string expr_compile(const std::string& expr) {
-  static std::mutex mu;
-  static std::map<std::string, std::string> cache;  // expression -> code object
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(expr);
-  if (it != cache.end()) return it->second;
-  const std::string src = expr_source(expr);
+namespace detail {
+std::string rtc_compile(const std::string& src, const std::string& expr) {
   hiprtcProgram prog = nullptr;
   hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "miint_expr.hip", 0, nullptr, nullptr);
   MIINT_CHECK(r == HIPRTC_SUCCESS, "hiprtcCreateProgram: " + rtc_error(r));
@@ -128,7 +123,17 @@ std::string expr_compile(const std::string& expr) {
   std::string code(code_n, '\0');
   MIINT_CHECK(hiprtcGetCode(prog, &code[0]) == HIPRTC_SUCCESS, "hiprtcGetCode");
   hiprtcDestroyProgram(&prog);
-  return cache[expr] = code;
+  return code;
+}
+}  // namespace detail
+
+std::string expr_compile(const std::string& expr) {
+  static std::mutex mu;
+  static std::map<std::string, std::string> cache;  // expression -> code object
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(expr);
+  if (it != cache.end()) return it->second;
+  return cache[expr] = detail::rtc_compile(expr_source(expr), expr);
 }
 
 ExprIntegrator::ExprIntegrator(const std::string& expr, int device, int grid)

@@ -13,6 +13,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -32,16 +33,37 @@ namespace {
 using SumFn = double (*)(double a, double h, double off, unsigned long long i0,
                          unsigned long long n);
 
-std::string host_source(const std::string& expr) {
+using SweepSumFn = double (*)(double a, double h, double off, unsigned long long i0,
+                              unsigned long long n, const double* p);
+
+// nparams < 0: f(x) (HostExpr). nparams >= 0: f(x, p0..p{nparams-1}) with the row's values
+// read from p (HostExprSweep); the sample loop is the same text.
+std::string host_source(const std::string& expr, int nparams = -1) {
+  std::string sig, load, args;
+  for (int j = 0; j < nparams; ++j) {
+    const std::string p = "p" + std::to_string(j);
+    sig += ", double " + p;
+    load += "  const double " + p + " = p[" + std::to_string(j) + "];\n";
+    args += ", " + p;
+  }
+  const std::string head =
+      nparams < 0
+          ? "static inline double miint_f(double x) { return (" + expr + "); }\n"
+          : "static inline double miint_fp(double x" + sig + ") { return (" + expr + "); }\n"
+            "#define miint_f(X) miint_fp((X)" + args + ")\n";
+  const std::string entry =
+      nparams < 0
+          ? "extern \"C\" double miint_host_expr_sum(double a, double h, double off, "
+            "unsigned long long i0,\n                                      unsigned long long n) {\n"
+          : "extern \"C\" double miint_host_expr_sweep_sum(double a, double h, double off, "
+            "unsigned long long i0,\n                                            "
+            "unsigned long long n, const double* p) {\n" + load;
   return R"(#include <cmath>
 using namespace std;
-static inline double miint_f(double x) { return ()" + expr + R"(); }
-// sum over i in [i0, i0 + n) of f(a + (i + off) h): blocks of 4096 samples, 8 accumulators
+)" + head + R"(// sum over i in [i0, i0 + n) of f(a + (i + off) h): blocks of 4096 samples, 8 accumulators
 // per block (independent: the compiler may vectorise what it can without reassociating),
 // block sums added with Kahan compensation
-extern "C" double miint_host_expr_sum(double a, double h, double off, unsigned long long i0,
-                                      unsigned long long n) {
-  double total = 0.0, comp = 0.0;
+)" + entry + R"(  double total = 0.0, comp = 0.0;
   for (unsigned long long done = 0; done < n;) {
     const unsigned long long m = n - done < 4096ull ? n - done : 4096ull;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -102,14 +124,15 @@ void check_not_profiled() {
 
 struct Compiled {
   void* handle = nullptr;
-  SumFn fn = nullptr;
+  void* fn = nullptr;  // SumFn (nparams < 0) or SweepSumFn
 };
 
-Compiled compile_host(const std::string& expr) {
+Compiled compile_host(const std::string& expr, int nparams = -1) {
   static std::mutex mu;
-  static std::map<std::string, Compiled> cache;
+  static std::map<std::pair<std::string, int>, Compiled> cache;
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(expr);
+  const auto key = std::make_pair(expr, nparams);
+  auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   expr_check(expr);
   const char* tmp = std::getenv("TMPDIR");
@@ -118,7 +141,7 @@ Compiled compile_host(const std::string& expr) {
   const std::string src = dir + "/f.cpp", so = dir + "/f.so", log = dir + "/log.txt";
   {
     std::ofstream f(src);
-    f << host_source(expr);
+    f << host_source(expr, nparams);
   }
   check_not_profiled();
   const int rc = run_child({host_compiler(), "-std=c++17", "-O3", "-march=native", "-fPIC",
@@ -141,16 +164,14 @@ Compiled compile_host(const std::string& expr) {
   const std::string dl_err = c.handle ? "" : ::dlerror();
   cleanup();
   MIINT_CHECK(c.handle != nullptr, "host expression: dlopen: " + dl_err);
-  c.fn = reinterpret_cast<SumFn>(::dlsym(c.handle, "miint_host_expr_sum"));
+  c.fn = ::dlsym(c.handle, nparams < 0 ? "miint_host_expr_sum" : "miint_host_expr_sweep_sum");
   MIINT_CHECK(c.fn != nullptr, "host expression: symbol missing");
-  return cache[expr] = c;
+  return cache[key] = c;
 }
 
 }  // namespace
 
-HostExpr::HostExpr(const std::string& expr) : expr_(expr) {
-  fn_ = reinterpret_cast<void*>(compile_host(expr).fn);
-}
+HostExpr::HostExpr(const std::string& expr) : expr_(expr) { fn_ = compile_host(expr).fn; }
 
 double HostExpr::integrate(double a, double b, uint64_t n, Rule rule, uint64_t begin,
                            uint64_t count, HostPool& pool) const {
@@ -168,6 +189,47 @@ double HostExpr::integrate(double a, double b, uint64_t n, Rule rule, uint64_t b
   double s = 0.0;
   for (int t = 0; t < T; ++t) s += part[t];  // thread order
   return s * h;
+}
+
+HostExprSweep::HostExprSweep(const std::string& expr, int nparams)
+    : expr_(expr), nparams_(nparams) {
+  MIINT_CHECK(nparams >= 0 && nparams <= kSweepMaxParams,
+              "host expression sweep: nparams must be 0..8");
+  fn_ = compile_host(expr, nparams).fn;
+}
+
+std::vector<double> HostExprSweep::integrate(const std::vector<double>& params, uint64_t rows,
+                                             double a, double b, uint64_t n, Rule rule,
+                                             uint64_t begin, uint64_t count,
+                                             HostPool& pool) const {
+  MIINT_CHECK(rows <= kSweepMaxRows, "host expression sweep: at most 2^20 rows");
+  MIINT_CHECK(params.size() == rows * static_cast<uint64_t>(nparams_),
+              "host expression sweep: " + std::to_string(params.size()) +
+                  " parameter values for " + std::to_string(rows) + " rows of " +
+                  std::to_string(nparams_));
+  for (double p : params)
+    MIINT_CHECK(std::isfinite(p), "host expression sweep: non-finite parameter");
+  MIINT_CHECK(n >= 1 && begin + count <= n && begin + count >= begin,
+              "host expression sweep slice outside [0, n)");
+  const SweepSumFn fn = reinterpret_cast<SweepSumFn>(fn_);
+  const double h = (b - a) / static_cast<double>(n), off = rule_offset(rule);
+  const int T = pool.threads();
+  std::vector<double> part(rows * T, 0.0);
+  // rows x thread slices: thread t takes slice t of every row (HostExpr's slices)
+  pool.run([&](int t) {
+    uint64_t tb = 0, tc = 0;
+    rank_slice(count, t, T, &tb, &tc);
+    if (!tc) return;
+    for (uint64_t k = 0; k < rows; ++k)
+      part[k * T + t] = fn(a, h, off, begin + tb, tc, params.data() + k * nparams_);
+  });
+  std::vector<double> out(rows);
+  for (uint64_t k = 0; k < rows; ++k) {
+    double s = 0.0;
+    for (int t = 0; t < T; ++t) s += part[k * T + t];  // thread order
+    out[k] = s * h;
+  }
+  return out;
 }
 
 }  // namespace miint

@@ -14,7 +14,9 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     ranks with rank-order TCP collectives (``backend="host"``, ``--device cpu``,
     ``python -m cuda_v_mpi_amd compare``);
   * any integrand at run time: one C++ expression over x compiled for gfx950 with hipRTC
-    (``ops.kernels.riemann_expr``, ``riemann --expr``).
+    (``ops.kernels.riemann_expr``, ``riemann --expr``), and parameter sweeps of it:
+    f(x, p0..p7) over K parameter rows per launch (``integrate_expr_sweep``,
+    ``riemann --expr ... --params FILE``).
 
 Layout: models/ (integrands), ops/ (kernel entry points), parallel/ (decomposition,
 process groups), utils/ (fixtures, oracles, output formats), integrate.py (high-level API).
@@ -25,4 +27,5 @@ __version__ = "0.1.0"
 
 from ._native import native, require_gpu  # noqa: F401
 from .integrate import IntegrationResult, Integrator, integrate, integrate_expr  # noqa: F401
+from .integrate import SweepResult, integrate_expr_sweep  # noqa: F401
 from .models import integrands  # noqa: F401

@@ -191,6 +191,27 @@ def cmd_integrate(a) -> int:
 
         lo = 0.0 if a.a is None else a.a
         hi = 1.0 if a.b is None else a.b
+        if a.params or a.linspace:  # a parameter sweep: f(x, p0..p7), K rows per launch
+            from . import integrate_expr_sweep
+            from ._native import native
+
+            if a.params and a.linspace:
+                raise SystemExit("integrate: give --params FILE or --linspace, not both")
+            m = native()
+            on_host = a.backend == "host" or a.device == "cpu"
+            rows = m.load_param_rows(a.params) if a.params else m.linspace_param_rows(a.linspace)
+            r = integrate_expr_sweep(a.expr, rows, lo, hi, n=int(a.n), rule=a.rule,
+                                     backend="host" if on_host else "hip")
+            if a.json:
+                rec = {"expr": a.expr, "a": lo, "b": hi, "n": int(a.n), "rule": a.rule,
+                       "rows": r.rows, "nparams": r.nparams, "values": r.values,
+                       "ms_per_sweep": r.seconds * 1e3,
+                       "subintervals_per_s": r.subintervals_per_s}
+                print(json.dumps(rec))
+            else:
+                for k, (row, v) in enumerate(zip(rows, r.values)):
+                    print(k, " ".join(f"{p:.17g}" for p in row), f"{v:.13g}")
+            return 0
         v = kernels.riemann_expr(a.expr, lo, hi, int(a.n), rule=a.rule)
         rec = {"expr": a.expr, "a": lo, "b": hi, "n": int(a.n), "rule": a.rule, "value": v}
         if a.analytic is not None:
@@ -312,6 +333,11 @@ def main(argv=None) -> int:
     ig.add_argument("--a", type=float, default=None)
     ig.add_argument("--b", type=float, default=None)
     ig.add_argument("--analytic", type=float, default=None)
+    ig.add_argument("--params", default="", help="--expr over x and p0..p7: a file of "
+                    "parameter rows (one per line), all rows in one launch")
+    ig.add_argument("--linspace", default="", help="p0=LO:HI:COUNT, a one-parameter sweep")
+    ig.add_argument("--device", default="gpu", choices=["gpu", "cpu"],
+                    help="sweeps: cpu = the host cores (as --backend host)")
     t2 = sub.add_parser("table2d")
     t2.add_argument("--grid", type=int, default=4096)
     t2.add_argument("--iters", type=int, default=100)

@@ -268,3 +268,65 @@ def integrate_expr(expr: str, a: float, b: float, n: int = 10**9, rule: str = "l
                              n=int(n), integrand=f"expr:{expr}", rule=rule, dtype="fp64",
                              gpus=ctx.world, seconds_wall=time.perf_counter() - t0,
                              seconds_device=dev_s)
+
+
+@dataclasses.dataclass
+class SweepResult:
+    values: list            # K values, one per parameter row
+    abs_err: list | None    # per row, when analytic values were given
+    rows: int
+    nparams: int
+    n: int
+    expr: str
+    rule: str
+    seconds: float          # the sweep call, rows in to values out (the compile is not in it)
+
+    @property
+    def subintervals_per_s(self) -> float:
+        return self.rows * self.n / self.seconds if self.seconds > 0 else float("nan")
+
+    def as_dict(self) -> dict:
+        d = dataclasses.asdict(self)
+        d.update(subintervals_per_s=self.subintervals_per_s)
+        return d
+
+
+def integrate_expr_sweep(expr: str, params, a: float, b: float, n: int = 10**6,
+                         rule: str = "left", backend: str = "hip", threads: int = 0,
+                         analytic=None) -> SweepResult:
+    """A parameter sweep: the integral of f(x, p0, ..., p{nparams-1}) on [a, b] for every row
+    of ``params`` (K x nparams; a list of rows or a 2-D array), the expression over ``x`` and
+    ``p0`` .. ``p7`` compiled once, all K rows in one launch (``backend="hip"``,
+    ``ops.kernels.riemann_expr_sweep``) or on the host cores (``backend="host"``).
+    ``analytic`` (a sequence of K values) adds the per-row error."""
+    from ._native import native
+    from .ops.kernels import _param_rows
+
+    if rule not in ("left", "mid", "right"):
+        raise ValueError("rule must be left|mid|right")
+    m = native()
+    p = _param_rows(params)
+    # the one compile stays outside the clock: it is per expression, not per sweep
+    if backend == "hip":
+        from .ops import kernels
+
+        m.expr_sweep_compile(expr, int(p.shape[1]))
+        t0 = time.perf_counter()
+        values = kernels.riemann_expr_sweep(expr, p, float(a), float(b), int(n), rule=rule)
+        values = [float(v) for v in values.cpu()]
+    elif backend == "host":
+        hs, pool = m.HostExprSweep(expr, p.shape[1]), m.HostPool(threads)
+        t0 = time.perf_counter()
+        values = [float(v) for v in hs.integrate(p, float(a), float(b), int(n),
+                                                 getattr(m.Rule, rule), 0, int(n), pool)]
+    else:
+        raise ValueError("integrate_expr_sweep backend must be 'hip' or 'host'")
+    secs = time.perf_counter() - t0
+    err = None
+    if analytic is not None:
+        want = [float(w) for w in analytic]
+        if len(want) != len(values):
+            raise ValueError(f"analytic has {len(want)} values for {len(values)} rows")
+        err = [abs(v - w) for v, w in zip(values, want)]
+    return SweepResult(values=values, abs_err=err, rows=len(values), nparams=int(p.shape[1]),
+                       n=int(n), expr=expr, rule=rule, seconds=secs)

@@ -363,3 +363,45 @@ def riemann_expr(expr: str, a: float, b: float, n: int, rule: str = "left",
     n_local = n - i_begin if n_local is None else n_local
     return ei.integrate(float(a), float(b), int(n), getattr(m.Rule, rule), int(i_begin),
                         int(n_local))
+
+
+_EXPR_SWEEP_CACHE: dict = {}
+
+
+def _param_rows(params):
+    """``params`` as a C-contiguous K x nparams float64 array (a list of K empty rows is
+    K x 0, an empty sequence 0 x 0)."""
+    import numpy as np
+
+    p = np.asarray(params, dtype=np.float64)
+    if p.ndim == 1 and p.size == 0:
+        p = p.reshape(0, 0)
+    if p.ndim != 2:
+        raise ValueError("params must be K rows of nparams numbers (2-D)")
+    return np.ascontiguousarray(p)
+
+
+def riemann_expr_sweep(expr: str, params, a: float, b: float, n: int, rule: str = "left",
+                       grid: int = 0, i_begin: int = 0,
+                       n_local: int | None = None) -> torch.Tensor:
+    """Riemann sums of f(x, p0, ..., p{nparams-1}) for K parameter rows in one launch:
+    ``params`` is K x nparams (a list of rows or a 2-D float64 array), the expression may
+    mention ``x`` and ``p0`` .. ``p7``. One hipRTC compile per (expression, nparams), cached
+    with its module per device; the rows are kernel data, so a new row costs no compile
+    (csrc/runtime/expr_sweep.cpp). Returns a 1-D fp64 tensor of the K values on the device;
+    a row's value does not depend on the rows that ride along. No rows (K = 0): an empty
+    tensor, nothing compiled or launched."""
+    m = native()
+    dev = _device()
+    p = _param_rows(params)
+    if p.shape[0] == 0:
+        return torch.empty(0, dtype=torch.float64, device=dev)
+    nparams = p.shape[1]
+    key = (expr, int(nparams), dev.index, int(grid))
+    es = _EXPR_SWEEP_CACHE.get(key)
+    if es is None:
+        es = _EXPR_SWEEP_CACHE[key] = m.ExprSweep(expr, int(nparams), dev.index, int(grid))
+    n_local = n - i_begin if n_local is None else n_local
+    vals = es.integrate(p, float(a), float(b), int(n), getattr(m.Rule, rule), int(i_begin),
+                        int(n_local))
+    return torch.as_tensor(vals, dtype=torch.float64).to(dev)
