@@ -84,6 +84,9 @@ size_t trainscan_workspace_bytes(uint64_t n);
 // workgroup; totals are then NOT written. Both calls must pass the same `fold`.
 void launch_trainscan_local(const TrainScanKernelParams& p, void* ws, double* totals,
                             hipStream_t s, bool fold = false);
+// Whether fold = true takes the fold variant for this slice (dt = 1/sps and at most 64 blocks
+// of 256 tiles); where it does not, both launchers run the hand-off form whatever `fold` says.
+bool trainscan_fold_applies(const TrainScanKernelParams& p);
 // K3: rank carries {C1, C2} from world x {T1, T2, count} gathered triples.
 void launch_trainscan_rank_carry(const double* gathered, int rank, double* carries,
                                  hipStream_t s);

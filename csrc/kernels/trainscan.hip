@@ -709,6 +709,8 @@ static bool use_fold(const TrainScanKernelParams& p, bool fold) {
   return fold && closed_form_sps(p.dt, &sps) && (nt + kB - 1) / kB <= kMaxFoldBlocks;
 }
 
+bool trainscan_fold_applies(const TrainScanKernelParams& p) { return use_fold(p, true); }
+
 void launch_trainscan_local(const TrainScanKernelParams& p, void* ws, double* totals,
                             hipStream_t s, bool fold) {
   MIINT_CHECK(p.n >= 1, "empty slice");

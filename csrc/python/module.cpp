@@ -622,12 +622,21 @@ PYBIND11_MODULE(_miint, m) {
         py::arg("extent") = 1800.0, py::arg("world") = 1);
   m.def("launch_trainscan", [](uintptr_t table, int tn, double dt, uint64_t i0, uint64_t n,
                                uint64_t win_lo, uint64_t win_hi, uintptr_t ws, uintptr_t totals,
-                               uintptr_t carries, uintptr_t vel, uintptr_t pos, uintptr_t s) {
+                               uintptr_t carries, uintptr_t vel, uintptr_t pos, uintptr_t s,
+                               bool fold) {
+    // fold = true: the one-GPU form TrainScan::enqueue_fused runs (per-workgroup fold of the
+    // block aggregates, totals not written) where it applies, else the hand-off as before
     TrainScanKernelParams p{ptr<const double>(table), tn, dt, i0, n, win_lo, win_hi};
-    launch_trainscan_local(p, ptr<void>(ws), ptr<double>(totals), stream(s));
+    launch_trainscan_local(p, ptr<void>(ws), ptr<double>(totals), stream(s), fold);
     launch_trainscan_write(p, ptr<const void>(ws), ptr<const double>(carries), ptr<double>(vel),
-                           ptr<double>(pos), stream(s));
-  });
+                           ptr<double>(pos), stream(s), fold);
+  }, py::arg("table"), py::arg("table_n"), py::arg("dt"), py::arg("i0"), py::arg("n"),
+     py::arg("win_lo"), py::arg("win_hi"), py::arg("ws"), py::arg("totals"), py::arg("carries"),
+     py::arg("vel"), py::arg("pos"), py::arg("stream"), py::arg("fold") = false);
+  m.def("trainscan_fold_applies", [](double dt, uint64_t n) {
+    TrainScanKernelParams p{nullptr, 2, dt, 0, n, 0, ~uint64_t(0)};
+    return trainscan_fold_applies(p);
+  }, "does launch_trainscan(fold = true) take the fold variant for this dt and slice length?");
   m.def("launch_trainscan_onepass", [](uintptr_t table, int tn, double dt, uint64_t i0,
                                        uint64_t n, uint64_t win_lo, uint64_t win_hi, uintptr_t ws,
                                        uintptr_t totals, uintptr_t vel, uintptr_t pos,

@@ -181,9 +181,21 @@ def profile_tensor(device=None) -> torch.Tensor:
     return _table_tensor(integrands.table(), torch.device(dev))
 
 
-def interp_fill(n: int, i0: int = 0, dt: float = 1e-4, out: torch.Tensor | None = None) -> torch.Tensor:
+def _scan_table(table: torch.Tensor | None, dev) -> torch.Tensor:
+    """The table a scan samples: the built-in profile, or a caller's contiguous fp64 device
+    tensor of 2..2048 entries at unit spacing."""
+    if table is None:
+        return profile_tensor(dev)
+    _check(table, name="table")
+    if table.dim() != 1:
+        raise ValueError("table must be one-dimensional")
+    return table
+
+
+def interp_fill(n: int, i0: int = 0, dt: float = 1e-4, out: torch.Tensor | None = None,
+                table: torch.Tensor | None = None) -> torch.Tensor:
     dev = _device()
-    tab = profile_tensor(dev)
+    tab = _scan_table(table, dev)
     out = torch.empty(n, dtype=torch.float64, device=dev) if out is None else out
     _check(out, name="out")
     native().launch_interp_fill(tab.data_ptr(), tab.numel(), dt, i0, n, out.data_ptr(), _stream())
@@ -208,10 +220,11 @@ def inclusive_scan(x: torch.Tensor, carry: torch.Tensor | None = None,
 
 
 def interp_scan(n: int, i0: int = 0, dt: float = 1e-4, window: tuple[int, int] | None = None,
-                carry: torch.Tensor | None = None) -> torch.Tensor:
+                carry: torch.Tensor | None = None,
+                table: torch.Tensor | None = None) -> torch.Tensor:
     """inclusive_scan(interp(profile, (i0+i)*dt)) fused in one pass."""
     dev = _device()
-    tab = profile_tensor(dev)
+    tab = _scan_table(table, dev)
     out = torch.empty(n, dtype=torch.float64, device=dev)
     st = _scan_state(n, dev)
     lo, hi = window if window is not None else (0, (1 << 64) - 1)
@@ -223,20 +236,29 @@ def interp_scan(n: int, i0: int = 0, dt: float = 1e-4, window: tuple[int, int] |
 
 
 def trainscan(n: int, i0: int = 0, dt: float = 1e-4, window: tuple[int, int] | None = None,
-              carries: torch.Tensor | None = None, algo: str = "fused"):
+              carries: torch.Tensor | None = None, algo: str = "fused",
+              table: torch.Tensor | None = None):
     """Two-phase scan of the interpolated profile (csrc/kernels/trainscan.hip).
 
     Returns (vel, pos, totals): vel = running sum of the samples, pos = running sum of vel,
     totals = {T1, T2} (the slice's sample sum and vel sum without carries). `carries`
     (2-element device tensor {C1, C2}) shifts the slice as if it followed earlier ranks
-    (algo="fused" only). algo="onepass": single pass with a decoupled look-back."""
-    if algo not in ("fused", "onepass"):
-        raise ValueError("algo must be fused|onepass")
+    (algo="fused" only). algo="onepass": single pass with a decoupled look-back.
+    algo="fold": the one-GPU form of "fused" that TrainScan runs without a communicator (the
+    write kernel folds the per-block aggregates itself); it takes no carries, writes no totals
+    (totals is None) and applies only to dt = 1/sps and at most 64 blocks of 256 tiles.
+    `table`: the table to sample instead of the built-in profile."""
+    if algo not in ("fused", "fold", "onepass"):
+        raise ValueError("algo must be fused|fold|onepass")
     if algo == "onepass" and carries is not None:
         raise ValueError("the one-pass scan takes no carries (single-GPU form)")
+    if algo == "fold" and carries is not None:
+        raise RuntimeError("fold mode is single-GPU (no rank carries)")
     m = native()
+    if algo == "fold" and not m.trainscan_fold_applies(dt, n):
+        raise RuntimeError("fold mode needs dt = 1/sps and at most 64 blocks of 256 tiles")
     dev = _device()
-    tab = profile_tensor(dev)
+    tab = _scan_table(table, dev)
     vel = torch.empty(n, dtype=torch.float64, device=dev)
     pos = torch.empty(n, dtype=torch.float64, device=dev)
     ws = torch.zeros(m.trainscan_workspace_bytes(n), dtype=torch.uint8, device=dev)  # zeroed once
@@ -250,8 +272,8 @@ def trainscan(n: int, i0: int = 0, dt: float = 1e-4, window: tuple[int, int] | N
         return vel, pos, totals
     m.launch_trainscan(tab.data_ptr(), tab.numel(), dt, i0, n, lo, hi, ws.data_ptr(),
                        totals.data_ptr(), carries.data_ptr() if carries is not None else 0,
-                       vel.data_ptr(), pos.data_ptr(), _stream())
-    return vel, pos, totals
+                       vel.data_ptr(), pos.data_ptr(), _stream(), algo == "fold")
+    return vel, pos, (None if algo == "fold" else totals)
 
 
 def _check_timeout(state: torch.Tensor) -> None:
