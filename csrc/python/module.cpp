@@ -533,6 +533,25 @@ PYBIND11_MODULE(_miint, m) {
     launch_table2d_chained(p, ptr<double>(partials), ptr<const double>(prev),
                            ptr<double>(prev_out), stream(s));
   });
+  // The multi-step row stream on a caller's table (Table2DPlan runs it on its own field):
+  // `steps` integrations in one launch of `phases` workgroups per block + the closing kernel;
+  // partials: steps x table2d_grid doubles, outs: steps doubles.
+  m.def("table2d_multistep_phases", [](int nx, int ny, double X, double Y, int gx, int gy,
+                                       int row0, int row1, int min_wg, int steps, int want) {
+    Table2DParams p{nullptr, nx, ny, X, Y, gx, gy, row0, row1, min_wg};
+    return table2d_multistep_phases(p, 0, steps, want);
+  }, py::arg("nx"), py::arg("ny"), py::arg("X"), py::arg("Y"), py::arg("gx"), py::arg("gy"),
+     py::arg("row0"), py::arg("row1"), py::arg("min_wg"), py::arg("steps"), py::arg("want") = 0);
+  m.def("launch_table2d_multistep", [](uintptr_t table, int nx, int ny, double X, double Y,
+                                        int gx, int gy, int row0, int row1, int min_wg,
+                                        uintptr_t partials, int steps, uintptr_t outs,
+                                        uintptr_t s, int phases) {
+    Table2DParams p{ptr<const double>(table), nx, ny, X, Y, gx, gy, row0, row1, min_wg};
+    launch_table2d_multistep(p, ptr<double>(partials), steps, ptr<double>(outs), stream(s),
+                             phases);
+  }, py::arg("table"), py::arg("nx"), py::arg("ny"), py::arg("X"), py::arg("Y"), py::arg("gx"),
+     py::arg("gy"), py::arg("row0"), py::arg("row1"), py::arg("min_wg"), py::arg("partials"),
+     py::arg("steps"), py::arg("outs"), py::arg("stream"), py::arg("phases") = 1);
   m.def("launch_table2d_finalize", [](uintptr_t partials, int n, uintptr_t out, uintptr_t s) {
     launch_table2d_finalize(ptr<const double>(partials), n, ptr<double>(out), stream(s));
   });

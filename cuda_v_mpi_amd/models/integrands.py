@@ -35,6 +35,7 @@ class IntegrandSpec:
     coef: tuple = ()
     p0: float = 0.0
     p1: float = 0.0
+    table: tuple = ()   # "table" only: the entries to interpolate (empty: the built-in profile)
 
     @property
     def native_id(self) -> int:
@@ -58,7 +59,7 @@ class IntegrandSpec:
             ts, vs = self.p0, self.p1
             return vs * ((b - ts * math.sin(b / ts)) - (a - ts * math.sin(a / ts)))
         if self.name == "table":
-            return fixtures.table_integral(a, b)
+            return fixtures.table_integral(a, b, self.table or None)
         raise ValueError(self.name)
 
     # ------------------------------------------------------------------ reference f(x)
@@ -79,7 +80,8 @@ class IntegrandSpec:
         if self.name == "train":
             return (1.0 - torch.cos(x / self.p0)) * self.p1
         if self.name == "table":
-            tab = torch.as_tensor(fixtures.profile_table(), dtype=torch.float64, device=x.device)
+            tab = torch.as_tensor(np.asarray(self.native_table()), dtype=torch.float64,
+                                  device=x.device)
             i = torch.clamp(x.floor().to(torch.int64), 0, tab.numel() - 2)
             fr = x - i.to(torch.float64)
             v0 = tab[i]
@@ -87,7 +89,9 @@ class IntegrandSpec:
         raise ValueError(self.name)
 
     def native_table(self) -> list:
-        return list(fixtures.profile_table()) if self.name == "table" else []
+        if self.name != "table":
+            return []
+        return list(self.table) if self.table else list(fixtures.profile_table())
 
 
 def pi4() -> IntegrandSpec:
@@ -102,8 +106,17 @@ def train() -> IntegrandSpec:
     return IntegrandSpec("train", 0.0, 1800.0, p0=TRAIN_TS, p1=TRAIN_VS)
 
 
-def table() -> IntegrandSpec:
-    return IntegrandSpec("table", 0.0, 1800.0)
+def table(profile: Sequence[float] | None = None, a: float | None = None,
+          b: float | None = None) -> IntegrandSpec:
+    """The built-in velocity profile on [0, 1800], or `profile`: 2..2048 entries at unit
+    spacing from x = 0, by default on [0, entries - 1]."""
+    if profile is None:
+        return IntegrandSpec("table", 0.0 if a is None else a, 1800.0 if b is None else b)
+    tab = tuple(float(v) for v in profile)
+    if not 2 <= len(tab) <= 2048:
+        raise ValueError("table supports 2..2048 entries")
+    return IntegrandSpec("table", 0.0 if a is None else a,
+                         float(len(tab) - 1) if b is None else b, table=tab)
 
 
 def poly(coef: Sequence[float] | None = None, degree: int = 6, seed: int = 0,

@@ -74,7 +74,7 @@ _TABLE_CACHE: dict = {}
 def _table_tensor(spec: IntegrandSpec, dev: torch.device):
     if spec.name != "table":
         return None
-    key = (dev.index,)
+    key = (dev.index, spec.table)  # per table: a second table must not get the first's tensor
     t = _TABLE_CACHE.get(key)
     if t is None:
         t = torch.tensor(spec.native_table(), dtype=torch.float64, device=dev)

@@ -115,12 +115,14 @@ def interp(table: np.ndarray, t):
     return table[i] + (table[i + 1] - table[i]) * fr
 
 
-def table_integral(a: float = 0.0, b: float = float(PROFILE_SECONDS)) -> float:
-    """Exact integral of the piecewise-linear interpolant over [a, b] (0 <= a <= b <= 1800)."""
-    v = _profile_tuple()
+def table_integral(a: float = 0.0, b: float = float(PROFILE_SECONDS), table=None) -> float:
+    """Exact integral of the piecewise-linear interpolant over [a, b] (0 <= a <= b <= 1800).
+    `table`: the entries to interpolate instead of the profile (unit spacing from 0; past
+    either end the end segment's line goes on, as the kernels' clamped segment has it)."""
+    v = _profile_tuple() if table is None else tuple(float(x) for x in table)
 
     def prim(t: float) -> float:
-        i = int(min(max(math.floor(t), 0), PROFILE_LEN - 2))
+        i = int(min(max(math.floor(t), 0), len(v) - 2))
         full = math.fsum(0.5 * (v[k] + v[k + 1]) for k in range(i))
         fr = t - i
         return full + fr * v[i] + 0.5 * fr * fr * (v[i + 1] - v[i])
