@@ -66,6 +66,7 @@ class ExprIntegrator {
   const std::string& expression() const { return expr_; }
 
  private:
+  void check(uint64_t n, uint64_t begin, uint64_t count) const;
   void enqueue(double a, double h, double off, uint64_t begin, uint64_t count, double scale,
                hipStream_t s);
   std::string expr_;
@@ -105,6 +106,9 @@ constexpr int kSweepMaxGrid = 2048;  // gx, and about gx * gy
 // (profiles/r8/expr_sweep.md): below 256 the per-row reduction shows (many small rows are
 // 3 % slower at 64, 14 % at 16), at 1024 a few middling rows leave most of the device idle.
 constexpr uint64_t kSweepMinSamplesPerLane = 256;
+// Partials held at once (doubles): rows beyond this many partials go in further chunks of
+// max(kSweepMaxPartials / gx, 1) rows.
+constexpr uint64_t kSweepMaxPartials = 1ull << 24;
 
 // Kernel source for f(x, p0..p{nparams-1}); a pJ at or above nparams fails in the compiler.
 std::string expr_sweep_source(const std::string& expr, int nparams);

@@ -730,6 +730,8 @@ PYBIND11_MODULE(_miint, m) {
         },
         py::arg("expr"), py::arg("nparams"),
         "compile a sweep expression for gfx950 with hipRTC (no device needed); the code object");
+  m.attr("SWEEP_MAX_GRID") = kSweepMaxGrid;
+  m.attr("SWEEP_MAX_PARTIALS") = kSweepMaxPartials;
   m.def("expr_sweep_shape", [](uint64_t n_local, uint64_t rows, int grid) {
           const SweepShape s = expr_sweep_shape(n_local, rows, grid);
           return py::make_tuple(s.gx, s.gy);

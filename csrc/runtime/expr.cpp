@@ -172,9 +172,21 @@ void ExprIntegrator::enqueue(double a, double h, double off, uint64_t begin, uin
                                   nullptr));
 }
 
+// Before anything is launched: the slice lies in [0, n) (begin + count may not wrap), and no
+// lane's share of it passes the kernel's 32-bit per-lane count (expr_sweep_shape's condition).
+void ExprIntegrator::check(uint64_t n, uint64_t begin, uint64_t count) const {
+  MIINT_CHECK(n >= 1 && begin + count <= n && begin + count >= begin,
+              "expression slice outside [0, n)");
+  const uint64_t lanes = static_cast<uint64_t>(grid_) * kExprBlock;
+  MIINT_CHECK(count / lanes + 1 < (1ull << 32),
+              "expression: " + std::to_string(count) + " samples over " + std::to_string(lanes) +
+                  " lanes pass the 32-bit per-lane count; use a larger grid or slice the "
+                  "samples");
+}
+
 double ExprIntegrator::integrate(double a, double b, uint64_t n, Rule rule, uint64_t begin,
                                  uint64_t count, double scale, const Comm* comm) {
-  MIINT_CHECK(n >= 1 && begin + count <= n, "expression slice outside [0, n)");
+  check(n, begin, count);
   DeviceGuard g(device_);
   const double h = (b - a) / static_cast<double>(n);
   hipStream_t s = stream_.get();
@@ -188,7 +200,8 @@ double ExprIntegrator::integrate(double a, double b, uint64_t n, Rule rule, uint
 double ExprIntegrator::time(double a, double b, uint64_t n, Rule rule, uint64_t begin,
                             uint64_t count, int iters, const std::function<void()>& at_start,
                             const std::function<void()>& at_end) {
-  MIINT_CHECK(iters >= 1 && n >= 1 && begin + count <= n, "bad expression timing request");
+  MIINT_CHECK(iters >= 1, "bad expression timing request");
+  check(n, begin, count);
   DeviceGuard g(device_);
   const double h = (b - a) / static_cast<double>(n);
   hipStream_t s = stream_.get();

@@ -13,8 +13,6 @@ namespace miint {
 
 namespace {
 constexpr int kSweepBlock = 256;
-// Partials held at once (doubles): rows beyond this many partials go in further chunks.
-constexpr uint64_t kSweepMaxPartials = 1ull << 24;
 
 void check_nparams(int nparams) {
   MIINT_CHECK(nparams >= 0 && nparams <= kSweepMaxParams,

@@ -1,7 +1,8 @@
 """Exact references of the Riemann-sum and 2-D field kernels, in integers only.
 
 The sibling of exact_scan.py for csrc/kernels/riemann.hip (table and polynomial integrands,
-integrands.hpp / integrands_f32.hpp) and the 2-D field kernels of csrc/kernels/table.hip.
+integrands.hpp / integrands_f32.hpp), the 2-D field kernels of csrc/kernels/table.hip and
+the run-time expression kernels (csrc/runtime/expr.cpp, expr_sweep.cpp, host_expr.cpp).
 With integer table entries or coefficients, a step h = 2**-k and a lower limit a =
 a_num / 2**(k+1), every sample coordinate, every sample value and every intermediate any
 kernel forms from them (tile midpoints, segment lines, kinks, Taylor shifts, pair sums,
@@ -242,6 +243,105 @@ def poly_budget_bits(coef, a_num: int, k: int, off2: int, i_begin: int, n: int,
         r = (r * xmax >> (k + 1)) + (c[j] << unit) + 1
         m = max(m, r)
     return {"fp64": _log2(wn * m), "fp32": _log2(F32_CHAIN * m)}
+
+
+# ------------------------------------------------------------------------------ expressions
+# The run-time expression kernels (csrc/runtime/expr.cpp, expr_sweep.cpp, host_expr.cpp) form
+# x = fma(idx, h, a) with an exact fp64 index, evaluate the user's expression and add. For an
+# expression that is a polynomial in x with integer coefficients the references are the
+# polynomial ones above; the bound below is the one that fits what such an expression does
+# (Horner in x, nothing else).
+def _num_max(a_num: int, begin: int, n: int) -> int:
+    """max |num_i| over samples [begin, begin + n) and all three rules (off2 in {0, 1, 2})."""
+    return max(abs(int(a_num) + 2 * begin), abs(int(a_num) + 2 * (begin + n - 1) + 2))
+
+
+def expr_budget_bits(coef, a_num: int, k: int, i_begin: int, n: int,
+                     whole_begin: int | None = None, whole_n: int | None = None) -> float:
+    """log2 of whole_n * max_i sum_j |c_j| max(|num_i|, 1)**j 2**((D - j) (k+1)), D = max(deg, 1),
+    over the samples of the whole rule (default: the slice) and any of the three rules.
+
+    A Horner step r <- r x + c_j on x = num / 2**(k+1) holds, in its own unit 2**-((deg-j)(k+1)),
+    at most sum_{i >= j} |c_i| |num|**(i-j) 2**((deg-i)(k+1)), which is no more than the sum
+    above (every term only gains factors max(|num|, 1) >= 1 and 2**(k+1) >= 1); the product
+    r x before c_j is added, and a step written with or without an fma, likewise. So the sum
+    bounds every intermediate of a sample in that intermediate's own unit, and whole_n times
+    it every partial sum of samples, in any order, of one launch or of all ranks together.
+    Sufficient, not tight. For sweep rows pass the element-wise largest |c_j| of the rows."""
+    _check_coords(k, 0, i_begin, n)
+    c = [abs(int(v)) for v in coef]
+    if any(float(v) != int(v) for v in coef):
+        raise ValueError("integer coefficients only")
+    deg = len(c) - 1
+    while deg > 0 and c[deg] == 0:
+        deg -= 1
+    D = max(deg, 1)
+    wb = i_begin if whole_begin is None else whole_begin
+    wn = n if whole_n is None else whole_n
+    x = max(_num_max(a_num, wb, wn), 1)
+    m = sum(c[j] * x ** j << ((D - j) * (k + 1)) for j in range(deg + 1))
+    return _log2(wn * m)
+
+
+def exact_absline_samples(p0_num: int, p1: int, p2: int, a_num: int, k: int, off2: int,
+                          i_begin: int, n: int) -> torch.Tensor:
+    """p2 + p1 |x_i - p0| with integer p1, p2 and the knot p0 = p0_num / 2**(k+1): int64 in
+    units of 2**-(k+1), p2 2**(k+1) + p1 |num_i - p0_num|. Not a polynomial: a sample that
+    sits one place off moves the sum by p1 units on one side of the knot and by -p1 on the
+    other, so a coordinate error cannot cancel as it can against a smooth integrand."""
+    _check_coords(k, off2, i_begin, n)
+    num = _nums(a_num, off2, i_begin, n)
+    return (int(p2) << (k + 1)) + int(p1) * (num - int(p0_num)).abs()
+
+
+def exact_absline_sum(p0_num: int, p1: int, p2: int, a_num: int, k: int, off2: int,
+                      i_begin: int, n: int) -> int:
+    return int(exact_absline_samples(p0_num, p1, p2, a_num, k, off2, i_begin, n).sum())
+
+
+def absline_budget_bits(p0_num: int, p1: int, p2: int, a_num: int, k: int, i_begin: int, n: int,
+                        whole_begin: int | None = None, whole_n: int | None = None) -> float:
+    """The analogue of expr_budget_bits for p2 + p1 fabs(x - p0), in units of 2**-(k+1):
+    log2 of whole_n * (|p2| 2**(k+1) + max(|p1|, 1) (max_i |num_i| + |p0_num|)). x, p0, x - p0,
+    its absolute value, p1 times it and that plus p2 are each at most the bracket."""
+    _check_coords(k, 0, i_begin, n)
+    wb = i_begin if whole_begin is None else whole_begin
+    wn = n if whole_n is None else whole_n
+    m = (abs(int(p2)) << (k + 1)) + max(abs(int(p1)), 1) * (_num_max(a_num, wb, wn) + abs(int(p0_num)))
+    return _log2(wn * m)
+
+
+def sample_moments(a_num: int, off2: int, i_begin: int, n: int) -> tuple[int, int]:
+    """(n, sum_i num_i) of samples [i_begin, i_begin + n), Python integers in closed form:
+    sum_i (a_num + off2 + 2 i) = n (a_num + off2) + 2 n i_begin + n (n - 1)."""
+    _check_coords(0, off2, i_begin, n)
+    return n, n * (int(a_num) + int(off2)) + 2 * n * i_begin + n * (n - 1)
+
+
+def exact_linear_rows_sums(rows, a_num: int, k: int, off2: int, i_begin: int,
+                           n: int) -> np.ndarray:
+    """Sums of many linear rows at once: row (p0, p1) is f(x) = p1 x + p0, and its samples
+    add up to p1 sum_i num_i + p0 n 2**(k+1) in units of 2**-(k+1). `rows` is K x 2 integers;
+    the two moments are taken once (sample_moments), the K sums are one int64 expression."""
+    _check_coords(k, off2, i_begin, n)
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+        raise ValueError("rows must be a K x 2 integer array of (p0, p1)")
+    r = r.astype(np.int64)
+    s0, s1 = sample_moments(a_num, off2, i_begin, n)
+    s0 <<= k + 1
+    pmax = int(np.abs(r).max()) if r.size else 0
+    if pmax * (abs(s0) + abs(s1)) >= 1 << 62:
+        raise ValueError("row sums past int64: no admissible case")
+    return r[:, 1] * np.int64(s1) + r[:, 0] * np.int64(s0)
+
+
+def values_f64(totals, unit_bits: int) -> np.ndarray:
+    """value_f64 of an int64 array (every entry below 2**53 in magnitude)."""
+    t = np.asarray(totals, dtype=np.int64)
+    if t.size and int(np.abs(t).max()) >= 1 << F64_BITS:
+        raise ValueError("a reference sum is past 2**53: no admissible case")
+    return np.ldexp(t.astype(np.float64), -int(unit_bits))
 
 
 # ------------------------------------------------------------------------------ 2-D field
