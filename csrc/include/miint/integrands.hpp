@@ -130,12 +130,16 @@ struct Pi4 : TileDefaults<Pi4> {
     asm volatile("" : "+v"(v));  // opaque -> stays a VGPR pair
     return v;
   }
+  // K2 = false leaves out the pk2 table (kSeriesExact never reads it: its squares take no
+  // pair curvature term); the opaque moves could not be dropped by the compiler.
+  template <bool K2 = true>
   __device__ __forceinline__ void init() {
 #pragma unroll
     for (int j = 0; j < kPairs; ++j) {
       pk[j] = opaque_s(j + 0.5);
       const double k2 = (j + 0.5) * (j + 0.5) - kMeanK2;
-      pk2[j] = j < kPk2Sgpr ? opaque_s(k2) : opaque_v(k2);
+      if constexpr (K2) pk2[j] = j < kPk2Sgpr ? opaque_s(k2) : opaque_v(k2);
+      else pk2[j] = k2;
     }
 #pragma unroll
     for (int i = 0; i < kSubs / 2; ++i) {
@@ -240,19 +244,28 @@ struct Pi4 : TileDefaults<Pi4> {
     return (M == DivMode::kSeries || M == DivMode::kSeriesExact) ? 0.5 * (U - 1) : 0.0;
   }
 
-  // kSeriesExact: the same seed, centres and per-sample residuals as kSeries, without the
-  // 1/2 offset — e_c = e_m + c0 A + (c0^2 + kMeanK2) B, e_{+-k} = e_c + (k^2 - kMeanK2) B
-  // +- k A' — and every sample's value is s (1 + e + e^2) at e's own precision (|e| <= 2e-6:
-  // its rounding is ~1e-22 absolute), rounded once, where kSeries's g = 1/2 + e rounds every
-  // sample at ulp(1/2) (up to 5 ulp from IEEE division).
-  // Cost (round 5): each sample forms its own residual e+-k and adds its
-  // own e^2 with one fma, exactly as kSeries forms g+-k and adds g^2 (whose square carries
-  // the linear term g^2 = 1/4 + e + e^2). The residuals' LINEAR terms are not added sample by
-  // sample: over the tile, e_u = e_m + k_u A + k_u^2 B with offsets k_u = u - (U-1)/2
-  // symmetric about the midpoint, so sum_u e_u = U e_m + B sum_u k_u^2 exactly (the A terms
-  // cancel) — one fma per tile, exact where per-sample adds would round. Per pair: c, e+, e-,
-  // two fma = 2.5 VALU per sample, kSeries's count (the first form, f = fma(e, e, e) and
-  // t += f per sample, was 3.5: +37 % time).
+  // kSeriesExact: the same seed and sub-tile centres as kSeries, without the 1/2 offset, and
+  // every sample's value is s (1 + e + e^2) at e's own precision (|e| <= 2e-6: its rounding
+  // is ~1e-22 absolute), where kSeries's g = 1/2 + e rounds every sample at ulp(1/2) (up to
+  // 5 ulp from IEEE division).
+  // The residuals' LINEAR terms are not added sample by sample: over the tile,
+  // e_u = e_m + k_u A + k_u^2 B with offsets k_u = u - (U-1)/2 symmetric about the midpoint,
+  // so sum_u e_u = U e_m + B sum_u k_u^2 exactly (the A terms cancel) — one fma per tile,
+  // exact where per-sample adds would round.
+  // Each sample then forms a residual of its own and adds its own e^2 with one fma. That
+  // residual is only ever squared, so it is taken LINEAR within its 32-sample sub-tile:
+  //   e_sq(+-k) = e_c +- k A',   e_c = e_m + c0 A + (c0^2 + kMeanK2) B,   A' = A + 2 c0 B,
+  // about the centre that carries the sub-tile's mean curvature. The sample's full residual
+  // is e = e_sq + (k^2 - kMeanK2) B; the square leaves that pair term out. Bound: |k^2 -
+  // kMeanK2| <= 15.5^2 - 85.25 = 155 and |B| = h^2 s, so |e - e_sq| <= 155 h^2 s. Every launch
+  // series_ok admits has 192 h <= 2e-6 and |e| <= 2e-6, hence |e^2 - e_sq^2| <= 2 |e| 155 h^2
+  // (+ second order) <= 2 * 2e-6 * 155 * (2e-6 / 192)^2 ~ 7e-20 of a value of order 1: about
+  // 1/1500 ulp per sample at the largest admitted h, ~1e-23 at N = 1e9; and as the pair
+  // terms sum to zero over a sub-tile, most of it cancels in the tile sum. (kSeries cannot do
+  // the same: its g^2 = 1/4 + e + e^2 carries the linear term inside the square.)
+  // Per pair: e+, e-, two fma = 2.0 VALU per sample (with the pair's c = e_c + (k^2 -
+  // kMeanK2) B: 2.5, kSeries's count, 1014 -> 822 VALU per tile; the first form,
+  // f = fma(e, e, e) and t += f per sample, was 3.5).
   // The seed's residual e_m = 1 - (1 + x_m^2) s is formed from the exact d_m (x_m s split
   // into q + qe by an fma): from the rounded d_m = fma(x_m, x_m, 1) it carried d_m's
   // rounding (up to ulp(1)/2 relative) into every sample of the tile — the 1.49-ulp maximum
@@ -302,49 +315,15 @@ struct Pi4 : TileDefaults<Pi4> {
       const double b2 = 2.0 * sd.b;
       // sum_u e_u (U e_m + B sum k^2), then every sample's e^2 on top (|t| <= ~1e-12)
       double t = fma(kSumK2, sd.b, static_cast<double>(U) * sd.em);
-#if MIINT_PI4_PIPE
-      // Software-pipelined by one pair: pair p+1's residuals are formed between pair p's two
-      // accumulations, so no instruction waits on the one issued just before it (at one
-      // wave per SIMD nothing else would fill that gap). Same operations, same order of the
-      // t accumulations: bitwise the plain loop's value. The empty asm statements pin the
-      // order (each takes the value just produced and the operand of the next instruction).
-      constexpr int kN = kSubs * kPairs;
-      double ec = centre_g(sd, 0), a = centre_slope(sd, b2, 0);
-      double c = fma(pk2[0], sd.b, ec);
-      double en = fma(-pk[0], a, c);
-      double ep = fma(pk[0], a, c);
-#pragma unroll
-      for (int p = 1; p < kN; ++p) {
-        const int q = p / kPairs, j = p % kPairs;
-        if (j == 0) {
-          ec = centre_g(sd, q);
-          a = centre_slope(sd, b2, q);
-        }
-        double c2 = fma(pk2[j], sd.b, ec);
-        asm volatile("" : "+v"(c2), "+v"(t));
-        t = fma(ep, ep, t);
-        asm volatile("" : "+v"(t), "+v"(c2));
-        double en2 = fma(-pk[j], a, c2);
-        asm volatile("" : "+v"(en2), "+v"(t));
-        t = fma(en, en, t);
-        asm volatile("" : "+v"(t), "+v"(c2));
-        double ep2 = fma(pk[j], a, c2);
-        asm volatile("" : "+v"(ep2), "+v"(ec));
-        en = en2;
-        ep = ep2;
-      }
-      t = fma(ep, ep, t);
-      t = fma(en, en, t);
-#else
 #pragma unroll
       for (int q = 0; q < kSubs; ++q) {
         const double ec = centre_g(sd, q);         // e at the centre (+ mean k^2 B)
         const double a = centre_slope(sd, b2, q);
 #pragma unroll
         for (int j = 0; j < kPairs; ++j) {
-          const double c = fma(pk2[j], sd.b, ec);
-          const double ep = fma(pk[j], a, c);   // sample kSub/2 + j's residual
-          const double en = fma(-pk[j], a, c);  // sample kSub/2 - 1 - j's
+          // the residuals to be squared: linear about the centre (no (k^2 - kMeanK2) B)
+          const double ep = fma(pk[j], a, ec);   // sample kSub/2 + j's
+          const double en = fma(-pk[j], a, ec);  // sample kSub/2 - 1 - j's
           t = fma(ep, ep, t);
           t = fma(en, en, t);
           // program order, as kSeries. (One chain even at 1 wave per SIMD: two running sums,
@@ -353,7 +332,6 @@ struct Pi4 : TileDefaults<Pi4> {
           asm volatile("" : "+v"(t));
         }
       }
-#endif
       // U samples of s (1 + e + e^2): s U + s (sum e + sum e^2)
       return fma(sd.s, t, fma(sd.s, static_cast<double>(U), acc));
     } else {
@@ -361,11 +339,16 @@ struct Pi4 : TileDefaults<Pi4> {
     }
   }
 
-  // kSeriesExact value of sample u of a full tile (validation kernel): s + s (e + e^2), one
-  // rounding, from the same seed, centre and residual e as the tile. The tile itself does
-  // not form this per-sample value: it adds the residuals' linear terms once per tile
-  // (s U + s (U e_m + B sum k^2 + sum e^2)), so the two differ by roundings only; over one
-  // full tile they agree to a few ulp of the tile sum
+  // kSeriesExact value of sample u of a full tile (validation kernel): s + s (e + e_sq^2),
+  // one rounding, from the same seed and centre as the tile. The linear term is the sample's
+  // full residual e = e_c + (k^2 - kMeanK2) B +- k A', curvature included — what the tile's
+  // closed-form sum U e_m + B sum k^2 adds up over its samples. The squared term is the
+  // residual the tile squares, e_sq = e_c +- k A', linear within the sub-tile: the square
+  // does not need the pair's curvature term, |e^2 - e_sq^2| <= 2 |e| 155 h^2 s ~ 7e-20 at the
+  // largest h series_ok admits (derivation above tile_acc). The tile itself does not form
+  // this per-sample value: it adds the linear terms once per tile
+  // (s U + s (U e_m + B sum k^2 + sum e_sq^2)), so the two differ by roundings only; over
+  // one full tile they agree to a few ulp of the tile sum
   // (test_pi4_series_exact_point_kernel_sums_to_the_tile).
   __device__ __forceinline__ double series_exact_point(double xm, double h, int u) const {
     const Seed sd = seed_exact(xm, h);
@@ -374,9 +357,12 @@ struct Pi4 : TileDefaults<Pi4> {
     const double ec = centre_g(sd, q);
     const double a = centre_slope(sd, b2, q);
     const int j = w >= kSub / 2 ? w - kSub / 2 : kSub / 2 - 1 - w;
-    const double c = fma(pk2[j], sd.b, ec);
-    const double e = w >= kSub / 2 ? fma(pk[j], a, c) : fma(-pk[j], a, c);
-    return fma(sd.s, fma(e, e, e), sd.s);
+    const double kj = w >= kSub / 2 ? pk[j] : -pk[j];
+    // linear term, curvature included: k^2 - kMeanK2 is exact (the kSeriesExact functor
+    // carries no pk2 table, see init)
+    const double e = fma(kj, a, fma(fma(kj, kj, -kMeanK2), sd.b, ec));
+    const double e_sq = fma(kj, a, ec);                   // the residual the tile squares
+    return fma(sd.s, fma(e_sq, e_sq, e), sd.s);
   }
 
   // Series value of sample u of a full tile, by exactly the operations tile_acc applies to

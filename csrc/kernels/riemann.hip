@@ -507,6 +507,10 @@ __device__ __forceinline__ F make_functor(const RiemannParams& p, const double* 
     return f;
   } else if constexpr (__is_same(F, Pi4) && M != DivMode::kSeries && M != DivMode::kSeriesExact) {
     return Pi4{};  // the register-pinned pair tables (Pi4::init) serve only the series tiles
+  } else if constexpr (__is_same(F, Pi4) && M == DivMode::kSeriesExact) {
+    Pi4 f;
+    f.init<false>();  // no k^2 table: these tiles square residuals linear in their sub-tile
+    return f;
   } else if constexpr (__is_same(F, Table) && M == DivMode::kSeries) {
     Table f{{}, table, n - 1};
     f.init();
