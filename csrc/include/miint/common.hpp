@@ -67,7 +67,9 @@ enum class Rule : int { kLeft = 0, kMid = 1, kRight = 2 };
 //   kSeriesExact   kSeries's residuals without the g = 1/2 + e fold: each sample's value is
 //                  s (1 + e + e^2) at e's own precision, the seed residual from the exact
 //                  d_m; the linear terms summed in closed form per tile, the squared residual
-//                  linear within its 32-sample sub-tile (2.16 VALU per sample; per point
+//                  linear within its 32-sample sub-tile and, with its square, formed in
+//                  packed fp32 (seed, centres, linear terms and sums fp64; at most 1.7e-18 of
+//                  the value, integrands.hpp) (1.23 VALU per sample; per point
 //                  from the true value max 1.34 ulp / mean 0.27 ulp on profiles/r5/accuracy_ab.md's windows, max 1.42 on the
 //                  bench record's 1/8-in window, <= 1.5 enforced by
 //                  test_pi4_series_exact_per_point_accuracy and the record's per_point check;

@@ -121,6 +121,10 @@ struct Pi4 : TileDefaults<Pi4> {
   double pc[kSubs / 2];      // |sub-tile centre offset| c0: 16, 48, 80 (SGPR)
   double pcm[kSubs / 2];     // c0 + kMeanK2 / c0                      (SGPR)
   double c15;                // 3/2 (e_m + 1/2 = 3/2 - d_m s in one fma)
+  // kSeriesExact's squares run in packed fp32 (tile_acc): (k_j, -k_j) as two floats in one
+  // SGPR pair, the scalar source of a v_pk_fma_f32 that forms both residuals of a pair.
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  f32x2 pkf[kPairs];         // (k_j, -k_j)                            (SGPR, K2 = false only)
 
   __device__ __forceinline__ static double opaque_s(double v) {
     asm volatile("" : "+s"(v));  // opaque -> stays an SGPR pair, never a literal
@@ -131,15 +135,21 @@ struct Pi4 : TileDefaults<Pi4> {
     return v;
   }
   // K2 = false leaves out the pk2 table (kSeriesExact never reads it: its squares take no
-  // pair curvature term); the opaque moves could not be dropped by the compiler.
+  // pair curvature term); the opaque moves could not be dropped by the compiler. It sets up
+  // the packed-float pair table instead, which only kSeriesExact reads.
   template <bool K2 = true>
   __device__ __forceinline__ void init() {
 #pragma unroll
     for (int j = 0; j < kPairs; ++j) {
       pk[j] = opaque_s(j + 0.5);
       const double k2 = (j + 0.5) * (j + 0.5) - kMeanK2;
-      if constexpr (K2) pk2[j] = j < kPk2Sgpr ? opaque_s(k2) : opaque_v(k2);
-      else pk2[j] = k2;
+      if constexpr (K2) {
+        pk2[j] = j < kPk2Sgpr ? opaque_s(k2) : opaque_v(k2);
+      } else {
+        pk2[j] = k2;
+        const f32x2 kk = {j + 0.5f, -(j + 0.5f)};
+        pkf[j] = __builtin_bit_cast(f32x2, opaque_s(__builtin_bit_cast(double, kk)));
+      }
     }
 #pragma unroll
     for (int i = 0; i < kSubs / 2; ++i) {
@@ -245,14 +255,14 @@ struct Pi4 : TileDefaults<Pi4> {
   }
 
   // kSeriesExact: the same seed and sub-tile centres as kSeries, without the 1/2 offset, and
-  // every sample's value is s (1 + e + e^2) at e's own precision (|e| <= 2e-6: its rounding
-  // is ~1e-22 absolute), where kSeries's g = 1/2 + e rounds every sample at ulp(1/2) (up to
+  // every sample's value is s (1 + e + e^2) with its linear residual at e's own fp64 precision
+  // (|e| <= 2e-6: its rounding is ~1e-22 absolute) and its e^2 formed in fp32 (below), where kSeries's g = 1/2 + e rounds every sample at ulp(1/2) (up to
   // 5 ulp from IEEE division).
   // The residuals' LINEAR terms are not added sample by sample: over the tile,
   // e_u = e_m + k_u A + k_u^2 B with offsets k_u = u - (U-1)/2 symmetric about the midpoint,
   // so sum_u e_u = U e_m + B sum_u k_u^2 exactly (the A terms cancel) — one fma per tile,
   // exact where per-sample adds would round.
-  // Each sample then forms a residual of its own and adds its own e^2 with one fma. That
+  // Each sample then forms a residual of its own and adds its own e^2. That
   // residual is only ever squared, so it is taken LINEAR within its 32-sample sub-tile:
   //   e_sq(+-k) = e_c +- k A',   e_c = e_m + c0 A + (c0^2 + kMeanK2) B,   A' = A + 2 c0 B,
   // about the centre that carries the sub-tile's mean curvature. The sample's full residual
@@ -263,9 +273,28 @@ struct Pi4 : TileDefaults<Pi4> {
   // 1/1500 ulp per sample at the largest admitted h, ~1e-23 at N = 1e9; and as the pair
   // terms sum to zero over a sub-tile, most of it cancels in the tile sum. (kSeries cannot do
   // the same: its g^2 = 1/4 + e + e^2 carries the linear term inside the square.)
-  // Per pair: e+, e-, two fma = 2.0 VALU per sample (with the pair's c = e_c + (k^2 -
-  // kMeanK2) B: 2.5, kSeries's count, 1014 -> 822 VALU per tile; the first form,
-  // f = fma(e, e, e) and t += f per sample, was 3.5).
+  // That squared residual and its square are formed in fp32; everything else of a sample is
+  // fp64: the seed and e_m, the centres e_c and slopes A' (converted once per sub-tile), the
+  // closed-form linear sum, and the fold of the tile into the lane accumulator. The squared
+  // term is the smallest part of s (1 + e + e^2): with |e_c|, |k A'| <= 2e-6 the two
+  // conversions and the fp32 fma leave |de| <= 3 * 2^-24 * 2e-6 ~ 3.6e-13, so
+  //   |d(e^2)| <= 2 |e| |de| + 2^-24 e^2 ~ 1.7e-18
+  // of a value of order 1 at the largest admitted h: under 1/60 ulp per sample (a numpy model
+  // of the tile: 1/180 there, ~1e-4 ulp at N = 1e9; on the GPU the benchmark's values at
+  // N = 1e9 are bitwise those of fp64 squares, profiles/r10/packed_squares_ab.md). fp32's
+  // range is no limit: e is a relative residual, independent of the size of x, e^2 <= 4e-12
+  // is far from overflow, and an e^2 below 1.2e-38, flushed or denormal, changes the value by
+  // less than 1e-38. The two fp32 running sums (the +k and the -k samples') hold at most
+  // 192 * 4e-12 each: their rounding over a tile is below 1e-14 absolute, against a tile sum
+  // of order 10^2.
+  // Per pair: (e+, e-) in one v_pk_fma_f32 from the SGPR pair (k, -k), their squares in a
+  // second = 1.0 VALU per sample, 466 per tile with the seed, the twelve centres, their 24
+  // conversions and the fold (gfx950 issues a v_pk_fma_f32 at the rate of a v_fma_f64: 57.1
+  // -> 35.2 us per 1e9; in fp64, two fma each: 2.0 per sample, 822 per tile; with the pair's
+  // c = e_c + (k^2 - kMeanK2) B: 2.5, kSeries's count, 1014; the first form, f = fma(e, e, e)
+  // and t += f per sample, was 3.5). The centres formed in packed fp32 too (three
+  // v_pk_fma_f32 per two sub-tiles, 428 per tile) measured 33.1 us, a difference of 4 times
+  // the run-to-run spread: not kept.
   // The seed's residual e_m = 1 - (1 + x_m^2) s is formed from the exact d_m (x_m s split
   // into q + qe by an fma): from the rounded d_m = fma(x_m, x_m, 1) it carried d_m's
   // rounding (up to ulp(1)/2 relative) into every sample of the tile — the 1.49-ulp maximum
@@ -313,25 +342,28 @@ struct Pi4 : TileDefaults<Pi4> {
       static_assert(U == kSeriesTile, "series tiles are kSubs sub-tiles of kSub samples");
       const Seed sd = seed_exact(xa, h);
       const double b2 = 2.0 * sd.b;
-      // sum_u e_u (U e_m + B sum k^2), then every sample's e^2 on top (|t| <= ~1e-12)
-      double t = fma(kSumK2, sd.b, static_cast<double>(U) * sd.em);
+      // sum_u e_u (U e_m + B sum k^2), in fp64
+      const double lin = fma(kSumK2, sd.b, static_cast<double>(U) * sd.em);
+      // every sample's e^2, in packed fp32: lane 0 the +k samples', lane 1 the -k samples'
+      f32x2 t2 = {0.0f, 0.0f};
 #pragma unroll
       for (int q = 0; q < kSubs; ++q) {
-        const double ec = centre_g(sd, q);         // e at the centre (+ mean k^2 B)
-        const double a = centre_slope(sd, b2, q);
+        // e at the centre (+ mean k^2 B) and the slope there: fp64, converted once
+        const f32x2 ec = static_cast<float>(centre_g(sd, q));
+        const f32x2 a = static_cast<float>(centre_slope(sd, b2, q));
 #pragma unroll
         for (int j = 0; j < kPairs; ++j) {
-          // the residuals to be squared: linear about the centre (no (k^2 - kMeanK2) B)
-          const double ep = fma(pk[j], a, ec);   // sample kSub/2 + j's
-          const double en = fma(-pk[j], a, ec);  // sample kSub/2 - 1 - j's
-          t = fma(ep, ep, t);
-          t = fma(en, en, t);
+          // the residuals to be squared: linear about the centre (no (k^2 - kMeanK2) B);
+          // samples kSub/2 + j and kSub/2 - 1 - j in one v_pk_fma_f32, their squares in another
+          const f32x2 e = __builtin_elementwise_fma(pkf[j], a, ec);
+          t2 = __builtin_elementwise_fma(e, e, t2);
           // program order, as kSeries. (One chain even at 1 wave per SIMD: two running sums,
           // e+ and e- apart, ran 4-5 % slower at G = 1 and at the 1/4 and 1/8 shares,
           // profiles/r6/batch_tail.md.)
-          asm volatile("" : "+v"(t));
+          asm volatile("" : "+v"(t2));
         }
       }
+      const double t = lin + (static_cast<double>(t2.x) + static_cast<double>(t2.y));
       // U samples of s (1 + e + e^2): s U + s (sum e + sum e^2)
       return fma(sd.s, t, fma(sd.s, static_cast<double>(U), acc));
     } else {
@@ -340,7 +372,8 @@ struct Pi4 : TileDefaults<Pi4> {
   }
 
   // kSeriesExact value of sample u of a full tile (validation kernel): s + s (e + e_sq^2),
-  // one rounding, from the same seed and centre as the tile. The linear term is the sample's
+  // from the same seed and centre as the tile; e_sq and its square in fp32 as the tile forms
+  // them (the product widened to double), everything else fp64. The linear term is the sample's
   // full residual e = e_c + (k^2 - kMeanK2) B +- k A', curvature included — what the tile's
   // closed-form sum U e_m + B sum k^2 adds up over its samples. The squared term is the
   // residual the tile squares, e_sq = e_c +- k A', linear within the sub-tile: the square
@@ -361,8 +394,10 @@ struct Pi4 : TileDefaults<Pi4> {
     // linear term, curvature included: k^2 - kMeanK2 is exact (the kSeriesExact functor
     // carries no pk2 table, see init)
     const double e = fma(kj, a, fma(fma(kj, kj, -kMeanK2), sd.b, ec));
-    const double e_sq = fma(kj, a, ec);                   // the residual the tile squares
-    return fma(sd.s, fma(e_sq, e_sq, e), sd.s);
+    // the residual the tile squares and its square, both in fp32 as the tile forms them
+    const float e_sq = fmaf(static_cast<float>(kj), static_cast<float>(a), static_cast<float>(ec));
+    const float sq = e_sq * e_sq;
+    return fma(sd.s, e + static_cast<double>(sq), sd.s);
   }
 
   // Series value of sample u of a full tile, by exactly the operations tile_acc applies to
