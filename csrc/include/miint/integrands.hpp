@@ -434,7 +434,13 @@ struct Pi4Wide : TileDefaults<Pi4Wide> {
 constexpr double kPi4NarrowMaxX = 0x1p249;
 
 // ------------------------------------------------------------------ tile seed: sin and cos
-// sin and cos of a tile midpoint angle (|theta| up to ~1e5; the integrands use [0, 2 pi]):
+// sin and cos of a tile midpoint angle, for |n| <= kTrigSeriesMaxN = 2^31 - 2^16 quadrants
+// (|theta| <= 3.3731e9; the dispatcher sends a launch with an end angle beyond it to the
+// per-sample tiles: kernels.hpp, trig_series_in_range). The quadrant is static_cast<int>(n),
+// which holds below 2^31 only and sets that limit; the reduction would carry further: its
+// first fma is exact (theta - n hi is a multiple of min(ulp(theta), 2^-32) below 1), the
+// second rounds once (<= 2^-54), and pi/2 - hi - lo = 3.6e-27 per quadrant adds 7.7e-18 at
+// |n| = 2^31, so r is within 6.3e-17 of the true reduced angle over the whole admitted range.
 // n = rint(theta 2/pi), r = theta - n pi/2 by a two-part Cody-Waite reduction (pi/2 = hi + lo,
 // hi with 33 significant bits, so n hi is exact and both fma steps round only at ulp(r)),
 // then the fdlibm kernel polynomials on [-pi/4, pi/4] (sin: odd degree 13; cos: even degree

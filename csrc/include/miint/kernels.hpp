@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -45,7 +46,8 @@ inline DivMode effective_div(DivMode d, double h) {
 // Per integrand: the sin / train-velocity series path (angle addition from a per-tile sincos
 // seed) and the table's segment-line tiles are exact for any h, so only the series/ieee
 // choice applies (kSeriesExact, the exact-grade request, is their series path); integrands
-// without a series path run kIeee.
+// without a series path run kIeee. (Any h, not any angle: sin and the train velocity leave the
+// series beyond kTrigSeriesMaxN quadrants, effective_div(params, ...) below.)
 inline bool series_request(DivMode d) { return d == DivMode::kSeries || d == DivMode::kSeriesExact; }
 inline DivMode effective_div(DivMode d, double h, Integrand f) {
   if (f == Integrand::kSin || f == Integrand::kTrainVel || f == Integrand::kTable)
@@ -66,13 +68,46 @@ inline DivMode effective_div(DivMode d, double h, Integrand f, DType t, int ncoe
     if (f == Integrand::kPi4) return series_ok_f32(h) ? DivMode::kSeries : DivMode::kIeee;
     if (f == Integrand::kPoly)
       return (ncoef >= 1 && ncoef <= kPolySeriesMaxCoeffs) ? DivMode::kSeries : DivMode::kIeee;
-    return DivMode::kSeries;  // sin, train velocity, table: exact for any h
+    return DivMode::kSeries;  // sin, train velocity, table: exact for any h (far angles: below)
   }
   if (f == Integrand::kPoly)  // the Taylor-pair tiles are exact-grade: kSeriesExact runs them
     return (series_request(d) && ncoef >= 1 && ncoef <= kPolySeriesMaxCoeffs)
                ? DivMode::kSeries
                : DivMode::kIeee;
   return effective_div(d, h, f);
+}
+
+// Far angles. The sin / train-velocity series tiles seed every tile with tile_sincos
+// (integrands.hpp): n = rint(theta 2/pi), a two-part Cody-Waite reduction and the quadrant
+// from static_cast<int>(n). The conversion holds for |n| < 2^31 only (|theta| < 3.373e9:
+// beyond it the hardware saturates and every tile gets one quadrant); the reduction itself is
+// off by 2^-54 (its one rounding; n hi is exact, hi has 33 bits) plus |n| 3.6e-27 (pi/2 - hi
+// - lo), which at |n| = 2^31 is 7.7e-18, an eighth of the rounding term, and would pass
+// 2^-54 only at |n| = 1.5e10. So the integer conversion sets the limit: the series tiles run
+// while both end angles of the launch (the extremes: theta is linear in the sample index, and
+// a tile's midpoint lies between its samples) have |n| <= 2^31 - 2^16, the 2^16 quadrants
+// (1e5 rad) of margin covering the device's own rounding of theta = x (1 / ts). A launch
+// beyond that runs the per-sample tiles (kIeee), whose trig_tile hands |n| > 65536 to ocml's
+// sin / cos (Payne-Hanek reduction: any finite angle); effective_div and the plan report it.
+// An fp32 launch beyond the limit runs the fp64 per-sample tiles: an fp32 coordinate there
+// has an ulp of 256, so there is no fp32 form of such a sample. NaN or infinite ends fail the
+// comparison, take the per-sample tiles and come out NaN from the library.
+constexpr double kTrigSeriesMaxN = 2147418112.0;  // 2^31 - 2^16 quadrants: |theta| <= 3.3731e9
+inline bool trig_series_in_range(const RiemannParams& p) {
+  const Integrand f = static_cast<Integrand>(p.integrand);
+  if (f != Integrand::kSin && f != Integrand::kTrainVel) return true;
+  const double first = static_cast<double>(p.i_begin) + p.off;
+  const double last = static_cast<double>(p.i_begin + (p.n > 0 ? p.n - 1 : 0)) + p.off;
+  const double w = f == Integrand::kTrainVel ? 1.0 / p.p0 : 1.0;
+  const double n0 = std::fabs(std::fma(first, p.h, p.a) * w) * 6.36619772367581382433e-01;
+  const double n1 = std::fabs(std::fma(last, p.h, p.a) * w) * 6.36619772367581382433e-01;
+  return n0 <= kTrigSeriesMaxN && n1 <= kTrigSeriesMaxN;
+}
+// The division a launch of `p` runs: the per-integrand choice above, and the per-sample tiles
+// for a sin / train launch with an end angle beyond kTrigSeriesMaxN quadrants.
+inline DivMode effective_div(const RiemannParams& p, DivMode d, DType t) {
+  const DivMode e = effective_div(d, p.h, static_cast<Integrand>(p.integrand), t, p.ncoef);
+  return (e != DivMode::kIeee && !trig_series_in_range(p)) ? DivMode::kIeee : e;
 }
 
 struct LaunchShape {

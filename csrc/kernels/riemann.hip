@@ -1151,12 +1151,15 @@ void dispatch(const RiemannParams& p, DType dtype, DivMode m, A&&... a) {
         else if (pi4_narrow(p, kPi4F32NarrowMaxX)) Op<DivMode::kIeee, Pi4F32>::run(a...);
         else Op<DivMode::kIeee, Pi4F32Wide>::run(a...);
         return;
+      // (beyond kTrigSeriesMaxN an fp32 coordinate has no angle left: the fp64 per-sample tiles)
       case Integrand::kSin:
         if (ser) Op<DivMode::kSeries, SinF32>::run(a...);
+        else if (!trig_series_in_range(p)) Op<DivMode::kIeee, Sin>::run(a...);
         else Op<DivMode::kIeee, SinF32>::run(a...);
         return;
       case Integrand::kTrainVel:
         if (ser) Op<DivMode::kSeries, TrainVelF32>::run(a...);
+        else if (!trig_series_in_range(p)) Op<DivMode::kIeee, TrainVel>::run(a...);
         else Op<DivMode::kIeee, TrainVelF32>::run(a...);
         return;
       case Integrand::kTable:
@@ -1281,10 +1284,6 @@ static void check_params(const RiemannParams& p, const double* table, int table_
   if (static_cast<Integrand>(f) == Integrand::kTrainVel)
     MIINT_CHECK(p.p0 != 0.0, "train integrand needs ts != 0");
   MIINT_CHECK(p.i_begin + p.n < (uint64_t(1) << 52), "sample index must stay below 2^52");
-}
-
-static DivMode effective_div(const RiemannParams& p, DivMode div, DType dtype) {
-  return miint::effective_div(div, p.h, static_cast<Integrand>(p.integrand), dtype, p.ncoef);
 }
 
 // Host-side constants of the angle-addition series (long double; AngleSeries in

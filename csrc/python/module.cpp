@@ -410,6 +410,22 @@ PYBIND11_MODULE(_miint, m) {
           launch_riemann_partials(p, dtype, div, {grid, kRiemannBlock}, ptr<const double>(table),
                                   table_n, ptr<double>(partials), stream(s));
         });
+  // read-only views of the dispatcher (no launch): the lane tile a launch of these parameters
+  // runs, and the division it runs (far sin / train angles included)
+  m.def("riemann_tile_len",
+        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div) {
+          return riemann_tile_len(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1),
+                                  dtype, div);
+        });
+  m.def("riemann_effective_div",
+        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div) {
+          return effective_div(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1), div,
+                               dtype);
+        });
+  m.attr("TRIG_SERIES_MAX_N") = kTrigSeriesMaxN;
+  m.attr("FAST_TRIG_MAX_N") = kFastTrigMaxN;
   m.def("launch_riemann_fused",
         [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
            std::vector<double> coef, double p0, double p1, DType dtype, DivMode div, int grid,

@@ -150,7 +150,7 @@ RiemannPlan::~RiemannPlan() {
 }
 
 DivMode RiemannPlan::effective_div() const {
-  return miint::effective_div(cfg_.div, params_.h, cfg_.integrand, cfg_.dtype, params_.ncoef);
+  return miint::effective_div(params_, cfg_.div, cfg_.dtype);  // far angles included
 }
 
 size_t RiemannPlan::graph_nodes() const {  // the largest captured batch graph

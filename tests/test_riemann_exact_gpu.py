@@ -13,7 +13,8 @@ cannot see it.
 
 The inputs live in riemann_exact_cases.py; test_exact_riemann_cpu.py shows on any box that
 each keeps its budget, so a mismatch here is a kernel finding, never an input problem.
-Out of reach of the method: sin, pi4, the train velocity and fp32acc have no exact inputs.
+Out of reach of the method: sin, pi4, the train velocity and fp32acc have no exact inputs
+(sin and the train velocity are held to a 200-bit truth instead: test_trig_truth_gpu.py).
 """
 from __future__ import annotations
 
