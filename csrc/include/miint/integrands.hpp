@@ -124,7 +124,14 @@ struct Pi4 : TileDefaults<Pi4> {
   // kSeriesExact's squares run in packed fp32 (tile_acc): (k_j, -k_j) as two floats in one
   // SGPR pair, the scalar source of a v_pk_fma_f32 that forms both residuals of a pair.
   typedef float f32x2 __attribute__((ext_vector_type(2)));
+#ifndef MIINT_PI4_PAIR_ORDER
+#define MIINT_PI4_PAIR_ORDER 1
+#endif
   f32x2 pkf[kPairs];         // (k_j, -k_j)                            (SGPR, K2 = false only)
+  // and the centres of the two sub-tiles at +c0 and -c0 are the two halves of one packed
+  // operation, from the same kind of pair:
+  f32x2 pcf[kSubs / 2];      // (c0, -c0)                              (SGPR, K2 = false only)
+  f32x2 pcmf[kSubs / 2];     // (c0 + kMeanK2 / c0, -(c0 + kMeanK2 / c0))        (likewise)
 
   __device__ __forceinline__ static double opaque_s(double v) {
     asm volatile("" : "+s"(v));  // opaque -> stays an SGPR pair, never a literal
@@ -156,6 +163,12 @@ struct Pi4 : TileDefaults<Pi4> {
       const double c0 = kSub * (i + 0.5);
       pc[i] = opaque_s(c0);
       pcm[i] = opaque_s(c0 + kMeanK2 / c0);
+      if constexpr (!K2) {
+        const float c0f = static_cast<float>(c0), cmf = static_cast<float>(c0 + kMeanK2 / c0);
+        const f32x2 cc = {c0f, -c0f}, cm = {cmf, -cmf};
+        pcf[i] = __builtin_bit_cast(f32x2, opaque_s(__builtin_bit_cast(double, cc)));
+        pcmf[i] = __builtin_bit_cast(f32x2, opaque_s(__builtin_bit_cast(double, cm)));
+      }
     }
     c15 = opaque_s(1.5);
   }
@@ -273,28 +286,39 @@ struct Pi4 : TileDefaults<Pi4> {
   // 1/1500 ulp per sample at the largest admitted h, ~1e-23 at N = 1e9; and as the pair
   // terms sum to zero over a sub-tile, most of it cancels in the tile sum. (kSeries cannot do
   // the same: its g^2 = 1/4 + e + e^2 carries the linear term inside the square.)
-  // That squared residual and its square are formed in fp32; everything else of a sample is
-  // fp64: the seed and e_m, the centres e_c and slopes A' (converted once per sub-tile), the
-  // closed-form linear sum, and the fold of the tile into the lane accumulator. The squared
-  // term is the smallest part of s (1 + e + e^2): with |e_c|, |k A'| <= 2e-6 the two
-  // conversions and the fp32 fma leave |de| <= 3 * 2^-24 * 2e-6 ~ 3.6e-13, so
-  //   |d(e^2)| <= 2 |e| |de| + 2^-24 e^2 ~ 1.7e-18
-  // of a value of order 1 at the largest admitted h: under 1/60 ulp per sample (a numpy model
-  // of the tile: 1/180 there, ~1e-4 ulp at N = 1e9; on the GPU the benchmark's values at
-  // N = 1e9 are bitwise those of fp64 squares, profiles/r10/packed_squares_ab.md). fp32's
-  // range is no limit: e is a relative residual, independent of the size of x, e^2 <= 4e-12
-  // is far from overflow, and an e^2 below 1.2e-38, flushed or denormal, changes the value by
-  // less than 1e-38. The two fp32 running sums (the +k and the -k samples') hold at most
-  // 192 * 4e-12 each: their rounding over a tile is below 1e-14 absolute, against a tile sum
-  // of order 10^2.
+  // That squared residual, the centre and slope it is formed from, and its square are fp32;
+  // everything else of a sample is fp64: the seed and e_m, the closed-form linear sum, and the
+  // fold of the tile into the lane accumulator. e_m, A, B and 2 B are rounded to fp32 once per
+  // tile (seed_f32), and the centres and slopes of the two sub-tiles at +c0 and -c0 are the two
+  // halves of three v_pk_fma_f32 on (c0, -c0) and (cm, -cm) SGPR pairs (centres_f32,
+  // slopes_f32); the pair loop reads its half through op_sel, without a move.
+  // Bound, with u = 2^-24 and E = 2e-6 >= |e_m| + 192 h (series_ok), 2 |x| s <= 1:
+  //   e_m, A, B -> fp32                   u |e_m|,  u |A|,  u |B|
+  //   in  = fma(cm, B, A)                 u |in|, |in| ~ |A|: with A's, times c0 <= 176:
+  //                                         2 u 176 h (the B terms: 176 * 177 h^2 u, < 1e-11 u)
+  //   e_c = fma(c0, in, e_m)              u |e_c| <= u E
+  //   A'  = fma(c0, 2 B, A)               u |A'| and A's u |A|, times k <= 15.5: 2 u 15.5 h
+  //   e   = fma(k, A', e_c)               u |e| <= u E
+  // in all |de| <= u (|e_m| + 383 h + 2 E) <= 4 u E ~ 4.8e-13 (3 u E with fp64 centres), so
+  //   |d(e^2)| <= 2 |e| |de| + u e^2 <= 1.9e-18 + 2.4e-19, and 7e-20 for the curvature: 2.2e-18
+  // of a value of order 1 at the largest admitted h: under 1/50 ulp per sample. (A numpy model
+  // of the tile against exact rational arithmetic, tests/test_pi4_packed_centres_cpu.py: 1/280
+  // ulp there at the worst, 1e-7 ulp at N = 1e10; on the GPU the benchmark's 48 step values at
+  // N = 1e9 are bitwise those of fp64 centres and of fp64 squares, profiles/r12/centres_ab.md.)
+  // fp32's range is no limit: e is a relative residual, independent of the size of x,
+  // e^2 <= 4e-12 is far from overflow, and an e^2 below 1.2e-38, flushed or denormal, changes
+  // the value by less than 1e-38. The fp32 running sums hold at most 192 * 4e-12 each: their
+  // rounding over a tile is below 1e-14 absolute, against a tile sum of order 10^2.
   // Per pair: (e+, e-) in one v_pk_fma_f32 from the SGPR pair (k, -k), their squares in a
-  // second = 1.0 VALU per sample, 466 per tile with the seed, the twelve centres, their 24
-  // conversions and the fold (gfx950 issues a v_pk_fma_f32 at the rate of a v_fma_f64: 57.1
-  // -> 35.2 us per 1e9; in fp64, two fma each: 2.0 per sample, 822 per tile; with the pair's
-  // c = e_c + (k^2 - kMeanK2) B: 2.5, kSeries's count, 1014; the first form, f = fma(e, e, e)
-  // and t += f per sample, was 3.5). The centres formed in packed fp32 too (three
-  // v_pk_fma_f32 per two sub-tiles, 428 per tile) measured 33.1 us, a difference of 4 times
-  // the run-to-run spread: not kept.
+  // second = 1.0 VALU per sample, 427 per tile (1.11 per sample) with the seed, the 18 packed
+  // FMAs of the centres, 3 conversions and the fold (gfx950 issues a v_pk_fma_f32 at the rate
+  // of a v_fma_f64; with the centres in fp64, three v_fma_f64 and two conversions per
+  // sub-tile: 466, 35.8 -> 33.3 us per 1e9; squares in fp64, two fma each: 822; with the pair's
+  // c = e_c + (k^2 - kMeanK2) B: 2.5 per sample, kSeries's count, 1014; the first form,
+  // f = fma(e, e, e) and t += f per sample, was 3.5). A = -2 h x_m s comes from the q = x_m s
+  // the exact e_m needs anyway (one multiplication less; A is only ever rounded to fp32).
+  // The pairs run in a pinned order, two at a time (subtile_squares below): 33.3 -> 32.2 us,
+  // and 5.91 -> 4.82 us at the 1.25e8-sample share of an 8-GPU step (one wave per SIMD).
   // The seed's residual e_m = 1 - (1 + x_m^2) s is formed from the exact d_m (x_m s split
   // into q + qe by an fma): from the rounded d_m = fma(x_m, x_m, 1) it carried d_m's
   // rounding (up to ulp(1)/2 relative) into every sample of the tile — the 1.49-ulp maximum
@@ -307,8 +331,88 @@ struct Pi4 : TileDefaults<Pi4> {
     // 1 - s is exact for s in [1/2, 2] (d in [1/2, 2]: x in [0, 1]); elsewhere the rounding
     // is no worse than 1 - d_m s's
     const double em = fma(-xm, qe, fma(-xm, q, 1.0 - s));
-    return {s, em, (-2.0 * h) * xm * s, -(h * h) * s};
+    // A = -2 h x_m s from the q already formed: one multiplication instead of two (A is only
+    // ever rounded to fp32, which hides the last fp64 place either way)
+    return {s, em, (-2.0 * h) * q, -(h * h) * s};
   }
+  // The seed's e_m, A, B and 2 B in fp32 (converted once per tile), and from them the
+  // centres and slopes of the two sub-tiles at +c0 and -c0 (pcf[i], pcmf[i]) together:
+  //   (e_c+, e_c-) = fma((c0, -c0), fma((cm, -cm), B, A), e_m),   (A'+, A'-) = fma((c0, -c0), 2 B, A)
+  struct SeedF32 {
+    float em, a, b, b2;
+  };
+  __device__ __forceinline__ static SeedF32 seed_f32(const Seed& sd) {
+    const float b = static_cast<float>(sd.b);
+    return {static_cast<float>(sd.em), static_cast<float>(sd.a), b, b + b};
+  }
+  __device__ __forceinline__ f32x2 centres_f32(const SeedF32& sf, int i) const {
+    const f32x2 in = __builtin_elementwise_fma(pcmf[i], f32x2{sf.b, sf.b}, f32x2{sf.a, sf.a});
+    return __builtin_elementwise_fma(pcf[i], in, f32x2{sf.em, sf.em});
+  }
+  __device__ __forceinline__ f32x2 slopes_f32(const SeedF32& sf, int i) const {
+    return __builtin_elementwise_fma(pcf[i], f32x2{sf.b2, sf.b2}, f32x2{sf.a, sf.a});
+  }
+
+  // The 16 +-k pairs of a sub-tile in a pinned order, two pairs at a time: both pairs'
+  // residuals, then both pairs' squares, the first pair's into ta and the second's into tb:
+  //   e0 = fma(k0, A', e_c)   e1 = fma(k1, A', e_c)   ta = fma(e0, e0, ta)   tb = fma(e1, e1, tb)
+  // and so on with k2, k3. No instruction reads a register that the instruction before it
+  // wrote. Left to the compiler, a pair's square follows its residual at once, and on gfx950
+  // it puts a wait state (s_nop 0) between the two: a wave on its own then issues two VALU in
+  // three turns. Inside an asm statement the compiler adds no wait states, and in this order
+  // none are needed; around the statement it adds its own (it takes every register the
+  // statement writes for one that needs the wait): 11 per tile where there were 192. The
+  // squares of successive pairs go to two running sums, added once per tile (v_pk_add_f32).
+  // With six or seven waves per SIMD the other waves fill a wave's wait states; a SIMD runs
+  // its last two waves alone for a quarter of a 48-step launch (profiles/r12/hazard_order.md).
+  // (Round 6's two running sums, 4-5 % slower, were fp64 chains, which have no such wait.)
+  // MIINT_PI4_PAIR_ORDER=0 builds the compiler's order with one sum (the A/B's other side).
+  // `a` and `c` hold the slopes and centres of the sub-tiles at +c0 (low halves) and -c0
+  // (high halves); Hi says which half both lanes of the residuals read (op_sel). First: the
+  // tile's first sub-tile, whose first squares start the sums (they add to an inline 0).
+#define MIINT_PAIRS2(K0, K1, SEL, TA, TB)                         \
+  "v_pk_fma_f32 %[e0], %[" K0 "], %[a], %[c]" SEL "\n\t"         \
+  "v_pk_fma_f32 %[e1], %[" K1 "], %[a], %[c]" SEL "\n\t"         \
+  "v_pk_fma_f32 %[ta], %[e0], %[e0], " TA "\n\t"                 \
+  "v_pk_fma_f32 %[tb], %[e1], %[e1], " TB "\n\t"
+#define MIINT_SUBTILE(SEL, TA0, TB0)                                                  \
+  MIINT_PAIRS2("k0", "k1", SEL, TA0, TB0) MIINT_PAIRS2("k2", "k3", SEL, "%[ta]", "%[tb]")       \
+  MIINT_PAIRS2("k4", "k5", SEL, "%[ta]", "%[tb]") MIINT_PAIRS2("k6", "k7", SEL, "%[ta]", "%[tb]")   \
+  MIINT_PAIRS2("k8", "k9", SEL, "%[ta]", "%[tb]") MIINT_PAIRS2("k10", "k11", SEL, "%[ta]", "%[tb]") \
+  MIINT_PAIRS2("k12", "k13", SEL, "%[ta]", "%[tb]") MIINT_PAIRS2("k14", "k15", SEL, "%[ta]", "%[tb]")
+#define MIINT_SUBTILE_IN                                                                      \
+  [k0] "s"(pkf[0]), [k1] "s"(pkf[1]), [k2] "s"(pkf[2]), [k3] "s"(pkf[3]), [k4] "s"(pkf[4]),   \
+  [k5] "s"(pkf[5]), [k6] "s"(pkf[6]), [k7] "s"(pkf[7]), [k8] "s"(pkf[8]), [k9] "s"(pkf[9]),   \
+  [k10] "s"(pkf[10]), [k11] "s"(pkf[11]), [k12] "s"(pkf[12]), [k13] "s"(pkf[13]),             \
+  [k14] "s"(pkf[14]), [k15] "s"(pkf[15]), [a] "v"(a), [c] "v"(c)
+#define MIINT_SEL_LO " op_sel_hi:[1,0,0]"
+#define MIINT_SEL_HI " op_sel:[0,1,1]"
+#define MIINT_ZERO "0 op_sel_hi:[1,1,0]"
+  template <bool Hi, bool First>
+  __device__ __forceinline__ void subtile_squares(f32x2& ta, f32x2& tb, f32x2 a, f32x2 c) const {
+    static_assert(kPairs == 16, "the statement names 16 pair constants");
+    f32x2 e0, e1;
+    if constexpr (First) {
+      static_assert(Hi, "a tile starts with the sub-tile at -176");
+      asm volatile(MIINT_SUBTILE(MIINT_SEL_HI, MIINT_ZERO, MIINT_ZERO)
+                   : [e0] "=&v"(e0), [e1] "=&v"(e1), [ta] "=&v"(ta), [tb] "=&v"(tb)
+                   : MIINT_SUBTILE_IN);
+    } else if constexpr (Hi) {
+      asm volatile(MIINT_SUBTILE(MIINT_SEL_HI, "%[ta]", "%[tb]")
+                   : [e0] "=&v"(e0), [e1] "=&v"(e1), [ta] "+v"(ta), [tb] "+v"(tb)
+                   : MIINT_SUBTILE_IN);
+    } else {
+      asm volatile(MIINT_SUBTILE(MIINT_SEL_LO, "%[ta]", "%[tb]")
+                   : [e0] "=&v"(e0), [e1] "=&v"(e1), [ta] "+v"(ta), [tb] "+v"(tb)
+                   : MIINT_SUBTILE_IN);
+    }
+  }
+#undef MIINT_PAIRS2
+#undef MIINT_SUBTILE
+#undef MIINT_SUBTILE_IN
+#undef MIINT_SEL_LO
+#undef MIINT_SEL_HI
+#undef MIINT_ZERO
 
   template <int U, DivMode M>
   __device__ __forceinline__ double tile_acc(double xa, double h, double acc) const {
@@ -341,28 +445,52 @@ struct Pi4 : TileDefaults<Pi4> {
     } else if constexpr (M == DivMode::kSeriesExact) {
       static_assert(U == kSeriesTile, "series tiles are kSubs sub-tiles of kSub samples");
       const Seed sd = seed_exact(xa, h);
-      const double b2 = 2.0 * sd.b;
       // sum_u e_u (U e_m + B sum k^2), in fp64
       const double lin = fma(kSumK2, sd.b, static_cast<double>(U) * sd.em);
+      const SeedF32 sf = seed_f32(sd);
       // every sample's e^2, in packed fp32: lane 0 the +k samples', lane 1 the -k samples'
       f32x2 t2 = {0.0f, 0.0f};
+      f32x2 ecs[kSubs / 2], aqs[kSubs / 2];
+#if MIINT_PI4_PAIR_ORDER
+      f32x2 tb;
 #pragma unroll
       for (int q = 0; q < kSubs; ++q) {
-        // e at the centre (+ mean k^2 B) and the slope there: fp64, converted once
-        const f32x2 ec = static_cast<float>(centre_g(sd, q));
-        const f32x2 a = static_cast<float>(centre_slope(sd, b2, q));
+        // e at the centre (+ mean k^2 B) and the slope there: sub-tile q < 6 sits at -c0 (the
+        // high halves, formed here together with the low halves that sub-tile 11 - q reads)
+        const int i = q < kSubs / 2 ? kSubs / 2 - 1 - q : q - kSubs / 2;
+        if (q < kSubs / 2) {
+          ecs[i] = centres_f32(sf, i);
+          aqs[i] = slopes_f32(sf, i);
+        }
+        if (q == 0) subtile_squares<true, true>(t2, tb, aqs[i], ecs[i]);
+        else if (q < kSubs / 2) subtile_squares<true, false>(t2, tb, aqs[i], ecs[i]);
+        else subtile_squares<false, false>(t2, tb, aqs[i], ecs[i]);
+      }
+      t2 += tb;
+#else
+#pragma unroll
+      for (int q = 0; q < kSubs; ++q) {
+        // e at the centre (+ mean k^2 B) and the slope there: sub-tile q < 6 sits at -c0 (the
+        // high halves, formed here together with the low halves that sub-tile 11 - q reads)
+        const int i = q < kSubs / 2 ? kSubs / 2 - 1 - q : q - kSubs / 2;
+        if (q < kSubs / 2) {
+          ecs[i] = centres_f32(sf, i);
+          aqs[i] = slopes_f32(sf, i);
+        }
+        const float ecq = q < kSubs / 2 ? ecs[i].y : ecs[i].x;
+        const float aq = q < kSubs / 2 ? aqs[i].y : aqs[i].x;
+        const f32x2 ec = {ecq, ecq}, a = {aq, aq};
 #pragma unroll
         for (int j = 0; j < kPairs; ++j) {
           // the residuals to be squared: linear about the centre (no (k^2 - kMeanK2) B);
           // samples kSub/2 + j and kSub/2 - 1 - j in one v_pk_fma_f32, their squares in another
           const f32x2 e = __builtin_elementwise_fma(pkf[j], a, ec);
           t2 = __builtin_elementwise_fma(e, e, t2);
-          // program order, as kSeries. (One chain even at 1 wave per SIMD: two running sums,
-          // e+ and e- apart, ran 4-5 % slower at G = 1 and at the 1/4 and 1/8 shares,
-          // profiles/r6/batch_tail.md.)
+          // program order, as kSeries
           asm volatile("" : "+v"(t2));
         }
       }
+#endif
       const double t = lin + (static_cast<double>(t2.x) + static_cast<double>(t2.y));
       // U samples of s (1 + e + e^2): s U + s (sum e + sum e^2)
       return fma(sd.s, t, fma(sd.s, static_cast<double>(U), acc));
@@ -395,7 +523,12 @@ struct Pi4 : TileDefaults<Pi4> {
     // carries no pk2 table, see init)
     const double e = fma(kj, a, fma(fma(kj, kj, -kMeanK2), sd.b, ec));
     // the residual the tile squares and its square, both in fp32 as the tile forms them
-    const float e_sq = fmaf(static_cast<float>(kj), static_cast<float>(a), static_cast<float>(ec));
+    // (centre and slope from the fp32 seed, the half of the +-c0 pair that sub-tile q reads)
+    const SeedF32 sf = seed_f32(sd);
+    const int i = q < kSubs / 2 ? kSubs / 2 - 1 - q : q - kSubs / 2;
+    const f32x2 ecs = centres_f32(sf, i), aqs = slopes_f32(sf, i);
+    const float e_sq = fmaf(static_cast<float>(kj), q < kSubs / 2 ? aqs.y : aqs.x,
+                            q < kSubs / 2 ? ecs.y : ecs.x);
     const float sq = e_sq * e_sq;
     return fma(sd.s, e + static_cast<double>(sq), sd.s);
   }
