@@ -103,11 +103,38 @@ inline bool trig_series_in_range(const RiemannParams& p) {
   const double n1 = std::fabs(std::fma(last, p.h, p.a) * w) * 6.36619772367581382433e-01;
   return n0 <= kTrigSeriesMaxN && n1 <= kTrigSeriesMaxN;
 }
+// Far coordinates of 4/(1+x^2). series_ok and its kin look at h alone, and the Pi4 series tiles
+// (integrands.hpp Pi4, riemann.hip Pi4F32 / Pi4F32Acc32) seed every tile with the hardware
+// reciprocal of d_m = 1 + x_m^2 in the tile's own format. The residuals are relative (|e| <=
+// |e_m| + (U/2) h at any |x|), so the tiles hold as long as d_m and 1/d_m are normal numbers
+// the reciprocal instruction takes and returns in full: in fp32 up to d_m = 2^126 (|x| = 2^63:
+// beyond it v_rcp_f32's result is denormal, and from |x| = 1.84e19 d_m is infinite, s = 0 and
+// e_m = fma(-inf, 0, 1) is NaN), in fp64 up to d_m = 2^1022 (|x| = 2^511; NaN from 1.34e154).
+// Such a launch needs h below ulp(x) / 2^52, so only a slice of a huge n or a degenerate
+// interval (a == b: h = 0) reaches it. A series request runs the series tiles while both end
+// coordinates of the launch (the extremes: x is linear in the sample index, a tile's midpoint
+// lies between its samples) stay below 2^62 in fp32 (the seed 1/d_m >= 2^-125: normal, with a
+// factor of four of room, and so is the fp32acc tile's 192 s) and below kPi4NarrowMaxX = 2^249
+// in fp64 (the range the IEEE tiles' narrow reciprocal is tested over, far inside 2^511);
+// beyond, the launch runs kIeee, where the dispatcher picks the full library division
+// (Pi4Wide, Pi4F32Wide; fp32acc has no wide form and refuses). NaN ends fail the comparison.
+constexpr double kPi4SeriesMaxX = 0x1p249;    // = kPi4NarrowMaxX (integrands.hpp)
+constexpr double kPi4SeriesMaxXF32 = 0x1p62;
+inline bool pi4_series_in_range(const RiemannParams& p, DType t) {
+  if (static_cast<Integrand>(p.integrand) != Integrand::kPi4) return true;
+  const double lim = is_fp32(t) ? kPi4SeriesMaxXF32 : kPi4SeriesMaxX;
+  const double first = static_cast<double>(p.i_begin) + p.off;
+  const double last = static_cast<double>(p.i_begin + (p.n > 0 ? p.n - 1 : 0)) + p.off;
+  return std::fabs(std::fma(first, p.h, p.a)) < lim && std::fabs(std::fma(last, p.h, p.a)) < lim;
+}
 // The division a launch of `p` runs: the per-integrand choice above, and the per-sample tiles
-// for a sin / train launch with an end angle beyond kTrigSeriesMaxN quadrants.
+// for a sin / train launch with an end angle beyond kTrigSeriesMaxN quadrants or a 4/(1+x^2)
+// launch with an end coordinate beyond the series tiles' range.
 inline DivMode effective_div(const RiemannParams& p, DivMode d, DType t) {
   const DivMode e = effective_div(d, p.h, static_cast<Integrand>(p.integrand), t, p.ncoef);
-  return (e != DivMode::kIeee && !trig_series_in_range(p)) ? DivMode::kIeee : e;
+  return (e != DivMode::kIeee && !(trig_series_in_range(p) && pi4_series_in_range(p, t)))
+             ? DivMode::kIeee
+             : e;
 }
 
 struct LaunchShape {
@@ -219,6 +246,10 @@ void launch_pi4_recip_narrow_f32(const float* d, uint64_t n, float* out, hipStre
 // Validation: when on, kIeee Pi4 launches run the library division everywhere (Pi4Wide,
 // Pi4F32Wide), so tests can check that the two give bitwise the same sums.
 void set_pi4_library_division(bool on);
+// Which kIeee 4/(1+x^2) tile a launch of `p` runs (read-only view of the dispatcher): true for
+// the narrow reciprocal (both end coordinates below 2^249 in fp64, 2^49 in fp32, and the
+// validation switch off), false for the library division (Pi4Wide, Pi4F32Wide; fp32acc refuses).
+bool pi4_ieee_narrow(const RiemannParams& p, DType dtype);
 // Validation switch: kIeee sin (Sin) and cos (TrainVel) by ocml per sample instead of the
 // fast per-sample path (fast_trig.hpp). Process-wide; tests only.
 void set_trig_library(bool on);

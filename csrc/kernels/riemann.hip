@@ -1455,6 +1455,9 @@ void launch_riemann_point_values(const RiemannParams& p, DivMode div, const doub
 }
 
 void set_pi4_library_division(bool on) { g_pi4_library_division.store(on); }
+bool pi4_ieee_narrow(const RiemannParams& p, DType dtype) {
+  return pi4_narrow(p, is_fp32(dtype) ? kPi4F32NarrowMaxX : kPi4NarrowMaxX);
+}
 void set_trig_library(bool on) { g_trig_library.store(on); }
 
 void launch_pi4_recip_narrow(const double* d, uint64_t n, double* out, hipStream_t stream) {

@@ -424,8 +424,16 @@ PYBIND11_MODULE(_miint, m) {
           return effective_div(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1), div,
                                dtype);
         });
+  m.def("riemann_pi4_ieee_narrow",
+        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+           std::vector<double> coef, double p0, double p1, DType dtype) {
+          return pi4_ieee_narrow(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1),
+                                 dtype);
+        });
   m.attr("TRIG_SERIES_MAX_N") = kTrigSeriesMaxN;
   m.attr("FAST_TRIG_MAX_N") = kFastTrigMaxN;
+  m.attr("PI4_SERIES_MAX_X") = kPi4SeriesMaxX;
+  m.attr("PI4_F32_SERIES_MAX_X") = kPi4SeriesMaxXF32;
   m.def("launch_riemann_fused",
         [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
            std::vector<double> coef, double p0, double p1, DType dtype, DivMode div, int grid,
