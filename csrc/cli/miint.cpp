@@ -40,6 +40,9 @@ struct BenchRow {
   bool multistep = false, close_in_launch = false, allreduce_to_host = false;
   BatchDiag diag;  // --diagnose: rank 0's diagnostic batch (diag.steps == 0 otherwise)
   std::string timeline_file;  // --timeline: where rank 0's timeline batch was written
+  std::string timeline_work;  // the form it records ("static" or "queue")
+  std::string work = "static";  // how multi-step batches deal their work (RiemannPlan::work)
+  int queue_workgroups = 0;
   cli::RankFacts facts;
   cli::Topology topo;
 };
@@ -100,8 +103,18 @@ void write_timeline(const std::string& path, const BatchTimeline& t, const Riema
   std::fputs("\"values\":[", f);
   for (size_t i = 0; i < t.values.size(); ++i)
     std::fprintf(f, i ? ",%.17g" : "%.17g", t.values[i]);
-  std::fputs("],\n\"stamps\":", f);
-  write_rows(f, t.stamps, static_cast<size_t>(t.steps) + 2);
+  std::fprintf(f, "],\n\"work\":\"%s\"", t.work.c_str());
+  if (t.work == "queue") {  // per physical workgroup and per item (BatchTimeline)
+    std::fprintf(f, ",\"workgroups\":%d,\n\"wg_stamps\":", t.workgroups);
+    write_rows(f, t.wg_stamps, 2);
+    std::fputs(",\n\"item_stamp\":", f);
+    write_rows(f, t.item_stamp, static_cast<size_t>(t.grid));
+    std::fputs(",\n\"item_owner\":", f);
+    write_rows(f, t.item_owner, static_cast<size_t>(t.grid));
+  } else {
+    std::fputs(",\n\"stamps\":", f);
+    write_rows(f, t.stamps, static_cast<size_t>(t.steps) + 2);
+  }
   std::fputs(",\n\"shader_clock\":", f);
   write_rows(f, t.shader_clock, 2);
   std::fputs(",\n\"hw\":", f);
@@ -145,8 +158,13 @@ BenchRow bench_one(const cli::Topology& topo, RiemannConfig cfg, int iters, bool
     // launch (RiemannPlan::timeline_batch). Collective like the diagnostic batch, so every
     // rank runs it; global rank 0's timeline is the one written (one writer, also when every
     // rank is a process of its own)
+    // The record is of the form the timed run ran (plan.work(): the queue's also where "auto"
+    // chose it), and the row says which.
+    std::string tl_work;
     if (!timeline.file.empty()) {
-      const BatchTimeline tl = plan.timeline_batch(std::min(iters, plan.config().slots));
+      const BatchTimeline tl =
+          plan.timeline_batch(std::min(iters, plan.config().slots), plan.work());
+      tl_work = tl.work;
       if (rank == 0)
         write_timeline(timeline.file, tl, cfg, timeline.integrand, timeline.dtype, timeline.div,
                        d.steps == tl.steps ? d.device_us : 0.0);
@@ -160,9 +178,12 @@ BenchRow bench_one(const cli::Topology& topo, RiemannConfig cfg, int iters, bool
       row.grid = plan.shape().grid;
       row.multistep = plan.multistep();
       row.close_in_launch = plan.close_in_launch();
+      row.work = plan.work();
+      row.queue_workgroups = plan.queue_workgroups();
       row.allreduce_to_host = plan.allreduce_to_host();
       row.diag = d;
       row.timeline_file = timeline.file;
+      row.timeline_work = tl_work;
     }
   });
   return row;
@@ -177,6 +198,8 @@ void print_row(const cli::Args& a, const BenchRow& r, const char* integ, const c
                    .add("grid", r.grid)
                    .add("multistep", r.multistep)
                    .add("close_in_launch", r.close_in_launch)
+                   .add("work", r.work)
+                   .add("queue_workgroups", r.queue_workgroups)
                    .add("allreduce_to_host", r.allreduce_to_host)
                    .add("ms_per_integration", r.ms)
                    .add("subintervals_per_s", r.n / (r.ms * 1e-3))
@@ -194,7 +217,8 @@ void print_row(const cli::Args& a, const BenchRow& r, const char* integ, const c
         .add("diag_device_us", r.diag.device_us)
         .add("diag_marker_us", r.diag.marker_us)
         .add("diag_host_us", r.diag.wall_us - r.diag.device_us);
-  if (!r.timeline_file.empty()) rec.add("timeline_file", r.timeline_file);
+  if (!r.timeline_file.empty())
+    rec.add("timeline_file", r.timeline_file).add("timeline_work", r.timeline_work);
   cli::emit(a, rec, true);
 }
 
@@ -323,6 +347,7 @@ constexpr const char* kUsage =
     "                   [--iters 200] [--gpus G] [--div series_exact|series|ieee] [--unfused] [--no-graph]\n"
     "                   [--block B] [--grid G] [--step-streams S] [--trig-library] [--settle N]\n"
     "                   [--no-multistep] [--slots K] [--close auto|kernel|launch] [--no-ar-host]\n"
+    "                   [--work auto|static|queue] [--queue-wg-per-cu W]\n"
     "                   [--diagnose] [--slice R/W] [--timeline FILE]\n"
     "                   (--timeline: after the timed run, one batch from the timeline build of\n"
     "                   the multi-step launch, per-workgroup device-clock stamps as JSON in FILE;\n"
@@ -373,6 +398,9 @@ int main(int argc, char** argv) {
       // kernel or the in-launch close; the bucketed all-reduce into pinned host slots or
       // into the device buffer and a copy
       c.close = a.str("close", c.close);
+      // A-B: the batch's work dealt statically or from the queue (MIINT_MS_WORK under auto)
+      c.work = a.str("work", c.work);
+      c.queue_wg_per_cu = static_cast<int>(a.integer("queue-wg-per-cu", 0));
       c.allreduce_to_host = !a.flag("no-ar-host");
       // --slice R/W: rank R's share of a W-GPU run's step, on this GPU
       cli::parse_slice(a, &c.slice_rank, &c.slice_world);

@@ -89,6 +89,19 @@ struct RiemannConfig {
   // Both give the same values bit for bit. Kernels under the 8-wave hint close by the kernel
   // whatever is asked (the close code would spill there).
   std::string close = "auto";
+  // How a kernel-closed multi-step batch deals its work to the launch's workgroups:
+  //   "static": workgroup b runs virtual block (b + s * rot) mod grid at step s
+  //             (launch_riemann_multistep);
+  //   "queue":  the resident workgroups pull (step, virtual block) items from one device
+  //             counter until none is left (launch_riemann_queue): every SIMD keeps its waves
+  //             until the work is gone and faster XCDs take more of it;
+  //   "auto":   the queue where the instantiation's own A/B showed it faster
+  //             (riemann_queue_pays), else static; the environment variable
+  //             MIINT_MS_WORK=static|queue overrides (the A/B's other side within one build).
+  // Both give the same values bit for bit (a partial depends only on its virtual block).
+  // Plans that close in the launch (close = "launch") keep the static kernel.
+  std::string work = "auto";
+  int queue_wg_per_cu = 0;  // queue: physical workgroups per CU (0: the occupancy query's)
   // Bucketed batches all-reduce their step values straight into the pinned host slots
   // (RCCL's receive buffer is the mapped host memory) instead of in place on the device
   // followed by a copy to pinned memory: one stream operation and one kernel boundary fewer.
@@ -103,6 +116,23 @@ struct RiemannConfig {
                                         // GPU rehearsal of a strong-scaled run's per-GPU work)
   double timeout_s = 300.0;    // collective watchdog in sync(); <= 0 disables
 };
+
+// RiemannConfig::work in effect ("static" or "queue"): `env` is the value of MIINT_MS_WORK (null
+// or empty: unset), `pays` riemann_queue_pays of the plan's instantiation, `keeps_static` true
+// for plans the queue does not apply to (no multi-step batches, or closed in the launch).
+inline std::string resolve_work(const std::string& work, const char* env, bool pays,
+                                bool keeps_static = false) {
+  MIINT_CHECK(work == "auto" || work == "static" || work == "queue",
+              "work must be auto, static or queue (got " + work + ")");
+  if (keeps_static) return "static";
+  if (work != "auto") return work;
+  if (env && *env) {
+    const std::string e(env);
+    MIINT_CHECK(e == "static" || e == "queue", "MIINT_MS_WORK must be static or queue (got " + e + ")");
+    return e;
+  }
+  return pays ? "queue" : "static";
+}
 
 // Balanced 64-bit slice of [0, n) for rank r of w: first (n % w) ranks get one extra.
 inline void rank_slice(uint64_t n, int r, int w, uint64_t* begin, uint64_t* count) {
@@ -179,6 +209,14 @@ struct BatchTimeline {
   std::vector<uint32_t> hw;            // [grid][2]: raw XCC_ID and HW_ID register words
   double device_us = 0.0;              // hipEvents around the instrumented launch + its close
   std::vector<double> values;          // the step values (host slots 0 .. steps-1)
+  // A queue plan's batch (RiemannConfig::work; launch_riemann_queue's timeline build): `grid`
+  // is the virtual grid, `workgroups` the physical workgroups that pulled from it;
+  // shader_clock and hw are [workgroups][2], `stamps` stays empty and these hold the record:
+  std::string work = "static";
+  int workgroups = 0;
+  std::vector<uint64_t> wg_stamps;     // [workgroups][2]: entry, exit
+  std::vector<uint64_t> item_stamp;    // [steps * grid]: after the item's block sum
+  std::vector<uint32_t> item_owner;    // [steps * grid]: the physical workgroup that ran it
 };
 constexpr uint64_t kTimelineUnsetStamp = 0;        // a cell no workgroup wrote
 constexpr uint32_t kTimelineUnsetId = 0xffffffffu;
@@ -254,7 +292,11 @@ class RiemannPlan {
   // would make the timeline describe another launch). That residency is the occupancy query's,
   // which can say more than the device holds at once (7 per CU where 6 entered together,
   // profiles/r7/timeline.md): tools/timeline_report.py counts the late entries from the stamps.
-  BatchTimeline timeline_batch(int nsteps);
+  // `form`: "static" (riemann_timeline_kernel: any multi-step plan, whatever its work),
+  // "queue" (riemann_queue_timeline_kernel: queue plans; no residency to refuse, late
+  // workgroups claim, fail and leave) or "auto": the queue's record for a plan built with
+  // work = "queue", the static launch's otherwise (BatchTimeline::work says which).
+  BatchTimeline timeline_batch(int nsteps, const std::string& form = "auto");
   // Collective: returns once every rank of the plan's communicator has entered (a 1-double
   // all-reduce, drained under the watchdog). No-op without a collective.
   void barrier();
@@ -284,6 +326,11 @@ class RiemannPlan {
   bool multistep() const { return chained() && multistep_; }
   // Multi-step batches are closed inside the persistent launch (RiemannConfig::close).
   bool close_in_launch() const { return multistep() && close_launch_; }
+  // How multi-step batches deal their work (RiemannConfig::work, in effect): "queue" or
+  // "static" (also for plans without multi-step batches: nothing is dealt from a queue).
+  const char* work() const { return multistep() && work_queue_ ? "queue" : "static"; }
+  // The queue launch's physical workgroups (0 for a static plan).
+  int queue_workgroups() const { return multistep() && work_queue_ ? queue_wgs_ : 0; }
   // Bucketed batches enqueued directly all-reduce into pinned host memory
   // (RiemannConfig::allreduce_to_host); captured batch graphs keep the device buffer + copy.
   // Off after check_allreduce_to_host found the transport unable to (every rank agrees).
@@ -327,6 +374,14 @@ class RiemannPlan {
   bool ar_host_ok_ = true;            // check_allreduce_to_host's verdict
   bool ar_host_checked_ = false;
   DeviceBuffer<unsigned int> ms_ticket_;  // its arrival counters (close_batch_in_launch)
+  bool work_queue_ = false;               // multistep batches dealt from the queue
+  int queue_wgs_ = 0;                     // its physical workgroups
+  DeviceBuffer<unsigned int> queue_;      // its head and exit count (kQueueWords, self-resetting)
+  void reset_queue() const;               // zero them (plan build; a failed or timed-out sync)
+  void enqueue_multistep(hipStream_t s, int nsteps, bool close_kernel) const;
+  // queue timeline buffers (timeline_batch of a queue plan; allocated at its first call)
+  DeviceBuffer<uint64_t> qtl_item_stamp_, qtl_wg_stamps_, qtl_shader_;
+  DeviceBuffer<uint32_t> qtl_item_owner_, qtl_hw_;
   // timeline_batch's buffers (allocated at its first call, sized for `slots` steps)
   DeviceBuffer<uint64_t> tl_stamps_, tl_shader_;
   DeviceBuffer<uint32_t> tl_hw_;

@@ -228,6 +228,35 @@ void launch_riemann_timeline(const RiemannParams& p, DType dtype, DivMode div,
                              hipStream_t stream, uint64_t* stamps, uint64_t* shader_clock,
                              uint32_t* hw, unsigned int* ticket = nullptr,
                              bool close_kernel = true);
+// The same K integrations dealt from a work queue (riemann.hip "work queue"): `workgroups`
+// physical workgroups pull items (step, virtual block) over the VIRTUAL grid shape.grid from
+// one device word until none is left, then the same closing kernel runs: partials[s][vb] and
+// out[s] are bit for bit launch_riemann_multistep's at the same shape. Any workgroups >= 1 is
+// correct (nobody waits for anybody); riemann_queue_grid(...) is the kernel's residency
+// (timeline = true: its timeline build's), 0 for the instantiations that keep chained batches.
+// `queue` holds kQueueWords words, zero before the first launch; the kernel's last workgroup
+// re-arms them, so launches (and graph replays) follow each other without a host reset. A
+// launch that failed or was abandoned leaves them undefined: zero them again.
+// riemann_queue_pays: RiemannConfig::work = "auto" runs the queue for this instantiation.
+constexpr int kQueueWords = 2 * kTicketStride;  // head and exit count, a 256-byte line each
+// `timeline` != nullptr: the timeline build of the launch. Thread 0 of the workgroup that
+// runs item i records the device clock after the item's block sum and its own index; every
+// physical workgroup its entry and exit (device clock, shader clock) and placement words.
+struct QueueTimeline {
+  uint64_t* item_stamp;    // [steps * grid]
+  uint32_t* item_owner;    // [steps * grid]
+  uint64_t* wg_stamps;     // [workgroups][2]
+  uint64_t* shader_clock;  // [workgroups][2]
+  uint32_t* hw;            // [workgroups][2] raw XCC_ID and HW_ID register words
+};
+int riemann_queue_grid(const RiemannParams& p, DType dtype, DivMode div, int block, int num_cus,
+                       bool timeline = false);
+bool riemann_queue_pays(const RiemannParams& p, DType dtype, DivMode div);
+void launch_riemann_queue(const RiemannParams& p, DType dtype, DivMode div, LaunchShape shape,
+                          int workgroups, const double* table, int table_n, double* partials,
+                          int steps, double scale, double* out, hipStream_t stream,
+                          unsigned int* queue, bool close_kernel = true,
+                          const QueueTimeline* timeline = nullptr);
 // The closing kernel of a multi-step launch on its own (launch_riemann_multistep with
 // close_kernel = false, e.g. to time the two apart): out[s] = scale * step s's sum.
 void launch_multistep_close(const double* partials, int grid, int steps, double scale,

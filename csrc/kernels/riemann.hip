@@ -682,8 +682,16 @@ __global__ __launch_bounds__(kMaxBlock) kFullOccupancy void riemann_chained_kern
 // work. multistep_close_kernel then closes all K steps at once (one workgroup per step,
 // index-ordered sums, the kernel boundary orders the partials): every step's value is the
 // fused / chained / two-kernel value at the same grid, bit for bit (a partial depends only on
-// its virtual block). The grid should be resident as a whole (riemann_multistep_grid): a
-// second round of workgroups would start only after the first finished every step.
+// its virtual block). The grid is capped at the occupancy query's residency
+// (riemann_multistep_grid), but that is not how the launch runs (profiles/r7/timeline.md,
+// r12/hazard_order.md, r14/queue_timeline.md, the headline at 7 workgroups per CU): six of the
+// seven workgroups of a CU enter together and the seventh when the first leaves; the oldest
+// workgroup takes nearly every issue slot and runs its steps at the whole CU's rate while the
+// others wait in their first step, so a CU's workgroups finish one after another (exits about
+// 205 us apart in a 48-step launch), a SIMD holds two or fewer waves for about a quarter of
+// the launch, and CUs of faster XCDs stand idle at the end. The values do not depend on any
+// of this; the schedule does, and the queue form below (RiemannConfig::work) deals the same
+// items so that every resident workgroup has work until none is left.
 // Each step re-derives its sample coordinates from p.a laundered through an empty asm, so
 // nothing of a step is loop-invariant: no step's work can be hoisted out of the loop or shared
 // with another, K steps are K full integrations.
@@ -926,6 +934,166 @@ constexpr bool multistep_pays() {
   return !(M == DivMode::kIeee && (__is_same(F, Pi4) || __is_same(F, Pi4Wide)));
 }
 
+// ---------------------------------------------------------------------------- work queue
+// The same K integrations dealt from a queue (RiemannConfig::work, "queue"): the launch's
+// P physical workgroups pull items i = s * nb + vb (step-major over the plan's VIRTUAL grid
+// nb) from one device word until none is left. A partial depends only on its virtual block,
+// so partials[s][vb] is bit for bit the static launch's whichever workgroup computes it, and
+// the closing kernel after it is the same. What changes is the schedule: every resident
+// workgroup has work until the items run out (a launch ends within about one item instead of
+// with the static launch's thin tail), and workgroups on faster XCDs take more items.
+//  * Thread 0 claims the NEXT item (one returning agent-scope add) at the start of the current
+//    one: the round trip runs under the item's tile loop, and its wait stands after it.
+//  * The claimed index reaches the other waves through an LDS word written before the block
+//    sum's barrier and read after it (two words alternating by seq & 1, as red[] and for the
+//    same reason): one barrier per item, as in the static kernel. One wave per workgroup: no
+//    barrier, a readfirstlane.
+//  * Nobody waits for anybody: a workgroup whose claim is >= steps * nb leaves (each makes
+//    exactly one such claim), so workgroups that become resident late, or never overlap with
+//    the others, are harmless.
+//  * On its way out thread 0 counts the workgroup on a second word (its own 256-byte line).
+//    Every workgroup's last claim returned before it counted itself, so the one that counts
+//    P - 1 knows both words are quiet and stores 0 to them; the kernel boundary orders that
+//    for the next launch (graph replays included). `queue` holds kQueueWords words, zero
+//    before the first launch.
+// A workgroup's items only grow, so the step of item i is counted up on the SALU (no division).
+struct QueueTimelineOut {
+  unsigned long long* item_stamp;    // [steps * nb] device clock after the item's block sum
+  unsigned* item_owner;              // [steps * nb] the physical workgroup that ran it
+  unsigned long long* wg_stamps;     // [P][2] device clock at entry and at exit
+  unsigned long long* shader_clock;  // [P][2] shader clock at entry and at exit
+  unsigned* hw;                      // [P][2] raw XCC_ID and HW_ID words
+};
+template <int T>
+__device__ __forceinline__ TileSplit tile_split(uint64_t n, unsigned nb) {
+  const uint32_t bs = blockDim.x;
+  const uint64_t lanes = static_cast<uint64_t>(nb) * bs;
+  const uint64_t ntile = n / T;
+  const uint64_t q = ntile / lanes;
+  return {lanes, q, bs, static_cast<uint32_t>(ntile - q * lanes)};
+}
+// The head is addressed with a zero offset taken from a VGPR (an empty asm, one v_mov inside
+// thread 0's branch): on a uniform address the compiler rewrites the add as one per wave and reads its
+// result back with a readfirstlane at once, i.e. it waits for the round trip where the claim
+// is made; with an address it cannot prove uniform the result stays in thread 0's register
+// and the wait goes to its first use.
+__device__ __forceinline__ unsigned queue_claim(unsigned* head) {
+  unsigned zero = 0;
+  asm volatile("" : "+v"(zero));
+  return __hip_atomic_fetch_add(head + zero, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <DivMode M, class F, bool TL = false>
+__device__ __forceinline__ void queue_body(const RiemannParams& p, const double* table,
+                                           int table_n, double* partials, int steps, unsigned nb,
+                                           unsigned* queue, QueueTimelineOut tl = {}) {
+  using Acc = typename AccOf<F>::type;
+  TimelineEntry te{};
+  if constexpr (TL) te = timeline_entry();
+  __shared__ double red[2][kMaxBlock / kWave];
+  __shared__ Acc red_acc[2][__is_same(Acc, double) ? 1 : kMaxBlock / kWave];
+  __shared__ unsigned next_item[2];
+  __shared__ double lds[lds_words<M, F>()];
+  const F f = make_functor<M, F>(p, table, table_n, lds);
+  const TileSplit sp = tile_split<F::template tile_len<M>()>(p.n, nb);  // the same every item
+  const unsigned total = static_cast<unsigned>(steps) * nb;
+  const bool one_wave = blockDim.x == kWave;
+  unsigned* head = queue;
+  unsigned* done = queue + kTicketStride;
+  // the first claim: nothing to hide it under
+  unsigned c = 0;
+  if (threadIdx.x == 0) c = queue_claim(head);
+  if (!one_wave) {
+    if (threadIdx.x == 0) next_item[1] = c;  // item 0 writes word 0
+    __syncthreads();
+    c = next_item[1];
+  }
+  unsigned i = __builtin_amdgcn_readfirstlane(c);
+  unsigned sbase = 0;  // s * nb of the step item i belongs to
+  for (unsigned seq = 0; i < total; ++seq) {
+    unsigned nxt = 0;
+    if (threadIdx.x == 0) nxt = queue_claim(head);  // waited for after the tile loop
+    while (i - sbase >= nb) sbase += nb;
+    const unsigned vb = i - sbase;
+    RiemannParams q = p;
+    asm volatile("" : "+s"(q.a));  // a fresh value every item (no instructions)
+    const Acc l = lane_sum<M>(q, f, vb, sp);
+    // The claim's wait, in every wave (free where no claim is in flight): left inside thread
+    // 0's branch below, the compiler must wait again where the branches join, before the
+    // register is reused, and there wave 0 would wait for its partial's store as well.
+    asm volatile("" : "+v"(nxt));
+    if (!one_wave && threadIdx.x == 0) next_item[seq & 1] = nxt;
+    double v;
+    if constexpr (__is_same(Acc, double)) v = block_sum_dyn(l, red[seq & 1]);
+    else v = static_cast<double>(block_sum_dyn(l, red_acc[seq & 1]));
+    if (threadIdx.x == 0) {
+      if constexpr (TL) {
+        unsigned wg = blockIdx.x;
+        asm volatile("" : "+v"(wg));  // as timeline_row: nothing of it kept across the loop
+        tl.item_stamp[i] = timeline_realtime_after(v);
+        tl.item_owner[i] = wg;
+      }
+      partials[i] = v;  // i = s * nb + vb
+    }
+    // past the block sum's barrier
+    i = __builtin_amdgcn_readfirstlane(one_wave ? nxt : next_item[seq & 1]);
+  }
+  if (threadIdx.x == 0) {
+    if constexpr (TL) {
+      const unsigned long long t = timeline_realtime();
+      unsigned long long* clk = timeline_row(tl.shader_clock, 2);
+      clk[0] = te.clk;
+      clk[1] = timeline_shader_clock();
+      unsigned long long* st = timeline_row(tl.wg_stamps, 2);
+      st[0] = te.t;
+      st[1] = t;
+      unsigned xcc, hw;
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+      unsigned* id = timeline_row(tl.hw, 2);
+      id[0] = xcc;
+      id[1] = hw;
+    }
+    const unsigned d = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (d == gridDim.x - 1) {  // the last one out: every claim has returned
+      __hip_atomic_store(head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) void riemann_queue_kernel(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps, unsigned nb,
+    unsigned* queue) {
+  queue_body<M, F>(p, table, table_n, partials, steps, nb, queue);
+}
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) kFullOccupancy void riemann_queue_kernel_o8(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps, unsigned nb,
+    unsigned* queue) {
+  queue_body<M, F>(p, table, table_n, partials, steps, nb, queue);
+}
+// The timeline build of the queue launch (see QueueTimelineOut).
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) void riemann_queue_timeline_kernel(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps, unsigned nb,
+    unsigned* queue, QueueTimelineOut tl) {
+  queue_body<M, F, true>(p, table, table_n, partials, steps, nb, queue, tl);
+}
+template <DivMode M, class F>
+__global__ __launch_bounds__(kMaxBlock) kFullOccupancy void riemann_queue_timeline_kernel_o8(
+    RiemannParams p, const double* table, int table_n, double* partials, int steps, unsigned nb,
+    unsigned* queue, QueueTimelineOut tl) {
+  queue_body<M, F, true>(p, table, table_n, partials, steps, nb, queue, tl);
+}
+// Instantiations whose plans deal their multi-step batches from the queue under
+// RiemannConfig::work = "auto": those whose own interleaved A/B against the static launch
+// showed every queue run faster (profiles/r14/queue_ab.md). The others keep the static launch
+// until they are measured.
+template <DivMode M, class F>
+constexpr bool queue_pays() {
+  return M == DivMode::kSeriesExact && __is_same(F, Pi4);
+}
+
 // Closes a multi-step launch: workgroup s sums step s's partials in index order (finalize
 // order) into out[s].
 __global__ __launch_bounds__(kMaxBlock) void multistep_close_kernel(const double* partials,
@@ -1117,6 +1285,47 @@ void timeline_per_cu_t(int block, int* out) {
   }
 }
 
+// The queue launch (every instantiation multistep_pays covers): `shape` is the VIRTUAL grid,
+// `wgs` the physical workgroups that pull from it.
+template <DivMode M, class F>
+void launch_queue_t(const RiemannParams& p, LaunchShape shape, int wgs, const double* table,
+                    int table_n, double* partials, int steps, unsigned* queue,
+                    const QueueTimelineOut* tl, hipStream_t stream) {
+  const unsigned nb = static_cast<unsigned>(shape.grid);
+  if constexpr (!multistep_pays<M, F>()) {
+    fail("this integrand/division keeps chained batches (no multi-step kernel, no queue)",
+         __FILE__, __LINE__);
+  } else if constexpr (multistep_o8<M, F>()) {
+    if (tl)
+      riemann_queue_timeline_kernel_o8<M, F><<<wgs, shape.block, 0, stream>>>(
+          p, table, table_n, partials, steps, nb, queue, *tl);
+    else
+      riemann_queue_kernel_o8<M, F><<<wgs, shape.block, 0, stream>>>(p, table, table_n, partials,
+                                                                     steps, nb, queue);
+  } else {
+    if (tl)
+      riemann_queue_timeline_kernel<M, F><<<wgs, shape.block, 0, stream>>>(
+          p, table, table_n, partials, steps, nb, queue, *tl);
+    else
+      riemann_queue_kernel<M, F><<<wgs, shape.block, 0, stream>>>(p, table, table_n, partials,
+                                                                  steps, nb, queue);
+  }
+}
+template <DivMode M, class F>
+void queue_per_cu_t(int block, bool timeline, int* out) {
+  *out = 0;
+  if constexpr (multistep_pays<M, F>()) {
+    const void* k;
+    if constexpr (multistep_o8<M, F>())
+      k = timeline ? reinterpret_cast<const void*>(&riemann_queue_timeline_kernel_o8<M, F>)
+                   : reinterpret_cast<const void*>(&riemann_queue_kernel_o8<M, F>);
+    else
+      k = timeline ? reinterpret_cast<const void*>(&riemann_queue_timeline_kernel<M, F>)
+                   : reinterpret_cast<const void*>(&riemann_queue_kernel<M, F>);
+    MIINT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(out, k, block, 0));
+  }
+}
+
 // kIeee Pi4 launches take Pi4::recip_narrow when both end coordinates (the extremes: x is
 // linear in the sample index) stay below kPi4NarrowMaxX in magnitude; NaN ends do not.
 std::atomic<bool> g_pi4_library_division{false};  // validation switch: always Pi4Wide
@@ -1234,6 +1443,15 @@ template <DivMode M, class F> struct TimelineOp {
 };
 template <DivMode M, class F> struct TimelineOccOp {
   static void run(int block, int* out) { timeline_per_cu_t<M, F>(block, out); }
+};
+template <DivMode M, class F> struct QueueOp {
+  template <class... A> static void run(A... a) { launch_queue_t<M, F>(a...); }
+};
+template <DivMode M, class F> struct QueueOccOp {
+  static void run(int block, bool timeline, int* out) { queue_per_cu_t<M, F>(block, timeline, out); }
+};
+template <DivMode M, class F> struct QueuePaysOp {
+  static void run(bool* out) { *out = multistep_pays<M, F>() && queue_pays<M, F>(); }
 };
 template <DivMode M, class F> struct TileLenOp {
   static void run(int* out) { *out = F::template tile_len<M>(); }
@@ -1432,6 +1650,48 @@ void launch_riemann_timeline(const RiemannParams& p, DType dtype, DivMode div,
                        reinterpret_cast<unsigned long long*>(shader_clock), hw};
   dispatch<TimelineOp>(p, dtype, eff, prepared(p, eff), shape, table, table_n, partials, steps,
                        rot, tl, stream);
+  MIINT_HIP(hipGetLastError());
+  if (!close_kernel) return;
+  launch_multistep_close(partials, shape.grid, steps, scale, out, shape.block, stream);
+}
+
+int riemann_queue_grid(const RiemannParams& p, DType dtype, DivMode div, int block, int num_cus,
+                       bool timeline) {
+  MIINT_CHECK(riemann_block_ok(block), "unsupported Riemann block size");
+  int per_cu = 0;
+  dispatch<QueueOccOp>(p, dtype, effective_div(p, div, dtype), block, timeline, &per_cu);
+  return per_cu * num_cus;  // 0: this instantiation runs chained batches
+}
+
+bool riemann_queue_pays(const RiemannParams& p, DType dtype, DivMode div) {
+  bool pays = false;
+  dispatch<QueuePaysOp>(p, dtype, effective_div(p, div, dtype), &pays);
+  return pays;
+}
+
+void launch_riemann_queue(const RiemannParams& p, DType dtype, DivMode div, LaunchShape shape,
+                          int workgroups, const double* table, int table_n, double* partials,
+                          int steps, double scale, double* out, hipStream_t stream,
+                          unsigned int* queue, bool close_kernel, const QueueTimeline* timeline) {
+  check_shape(shape);
+  check_params(p, table, table_n);
+  MIINT_CHECK(workgroups >= 1 && workgroups <= (1 << 20), "queue launch: workgroups out of range");
+  MIINT_CHECK(steps >= 1 && steps <= kMaxMultiSteps, "queue launch: 1..64 steps");
+  MIINT_CHECK(partials != nullptr && out != nullptr && queue != nullptr,
+              "queue launch needs partials, results and the queue words");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stamp words are 64-bit");
+  QueueTimelineOut tl{};
+  if (timeline) {
+    MIINT_CHECK(timeline->item_stamp && timeline->item_owner && timeline->wg_stamps &&
+                    timeline->shader_clock && timeline->hw,
+                "queue timeline launch needs its five buffers");
+    tl = {reinterpret_cast<unsigned long long*>(timeline->item_stamp), timeline->item_owner,
+          reinterpret_cast<unsigned long long*>(timeline->wg_stamps),
+          reinterpret_cast<unsigned long long*>(timeline->shader_clock), timeline->hw};
+  }
+  const DivMode eff = effective_div(p, div, dtype);
+  dispatch<QueueOp>(p, dtype, eff, prepared(p, eff), shape, workgroups, table, table_n, partials,
+                    steps, queue, timeline ? &tl : nullptr, stream);
   MIINT_HIP(hipGetLastError());
   if (!close_kernel) return;
   launch_multistep_close(partials, shape.grid, steps, scale, out, shape.block, stream);

@@ -280,6 +280,8 @@ PYBIND11_MODULE(_miint, m) {
       .def_readwrite("timeout_s", &RiemannConfig::timeout_s)
       .def_readwrite("host_direct", &RiemannConfig::host_direct)
       .def_readwrite("close", &RiemannConfig::close)
+      .def_readwrite("work", &RiemannConfig::work)
+      .def_readwrite("queue_wg_per_cu", &RiemannConfig::queue_wg_per_cu)
       .def_readwrite("allreduce_to_host", &RiemannConfig::allreduce_to_host)
       .def_readwrite("chain", &RiemannConfig::chain);
 
@@ -358,11 +360,11 @@ PYBIND11_MODULE(_miint, m) {
              r["wall_us"] = d.wall_us;
              return r;
            }, py::arg("steps"))
-      .def("timeline_batch", [](RiemannPlan& p, int steps) {
+      .def("timeline_batch", [](RiemannPlan& p, int steps, const std::string& form) {
              BatchTimeline t;
              {
                py::gil_scoped_release nogil;
-               t = p.timeline_batch(steps);
+               t = p.timeline_batch(steps, form);
              }
              // numpy arrays (copies): stamps [grid, steps + 2], shader_clock and hw [grid, 2]
              auto arr64 = [](const std::vector<uint64_t>& v, py::ssize_t rows, py::ssize_t cols) {
@@ -370,7 +372,10 @@ PYBIND11_MODULE(_miint, m) {
                std::copy(v.begin(), v.end(), a.mutable_data());
                return a;
              };
-             py::array_t<uint32_t> hw({static_cast<py::ssize_t>(t.grid), py::ssize_t(2)});
+             // a queue plan's record is per physical workgroup and per item (BatchTimeline)
+             const bool queue = t.work == "queue";
+             const py::ssize_t rows = queue ? t.workgroups : t.grid;
+             py::array_t<uint32_t> hw({rows, py::ssize_t(2)});
              std::copy(t.hw.begin(), t.hw.end(), hw.mutable_data());
              py::dict r;
              r["steps"] = t.steps;
@@ -378,12 +383,23 @@ PYBIND11_MODULE(_miint, m) {
              r["block"] = t.block;
              r["clock_khz"] = t.clock_khz;
              r["device_us"] = t.device_us;
-             r["stamps"] = arr64(t.stamps, t.grid, t.steps + 2);
-             r["shader_clock"] = arr64(t.shader_clock, t.grid, 2);
+             r["work"] = t.work;
+             if (queue) {
+               r["workgroups"] = t.workgroups;
+               r["wg_stamps"] = arr64(t.wg_stamps, rows, 2);
+               r["item_stamp"] = arr64(t.item_stamp, t.steps, t.grid);
+               py::array_t<uint32_t> owner({static_cast<py::ssize_t>(t.steps),
+                                            static_cast<py::ssize_t>(t.grid)});
+               std::copy(t.item_owner.begin(), t.item_owner.end(), owner.mutable_data());
+               r["item_owner"] = owner;
+             } else {
+               r["stamps"] = arr64(t.stamps, t.grid, t.steps + 2);
+             }
+             r["shader_clock"] = arr64(t.shader_clock, rows, 2);
              r["hw"] = hw;
              r["values"] = t.values;
              return r;
-           }, py::arg("steps"))
+           }, py::arg("steps"), py::arg("form") = "auto")
       .def("host_result", &RiemannPlan::host_result)
       .def_property_readonly("host_capacity", &RiemannPlan::host_capacity)
       .def_property_readonly("slots", &RiemannPlan::slots)
@@ -391,6 +407,8 @@ PYBIND11_MODULE(_miint, m) {
       .def_property_readonly("chained", &RiemannPlan::chained)
       .def_property_readonly("multistep", &RiemannPlan::multistep)
       .def_property_readonly("close_in_launch", &RiemannPlan::close_in_launch)
+      .def_property_readonly("work", [](const RiemannPlan& p) { return std::string(p.work()); })
+      .def_property_readonly("queue_workgroups", &RiemannPlan::queue_workgroups)
       .def_property_readonly("allreduce_to_host", &RiemannPlan::allreduce_to_host)
       .def_property_readonly("direct", &RiemannPlan::direct)
       .def_property_readonly("graph_nodes", &RiemannPlan::graph_nodes)
@@ -429,6 +447,20 @@ PYBIND11_MODULE(_miint, m) {
            std::vector<double> coef, double p0, double p1, DType dtype) {
           return pi4_ieee_narrow(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1),
                                  dtype);
+        });
+  // RiemannConfig::work in effect (no device needed): the plan's own resolution
+  m.def("resolve_work",
+        [](const std::string& work, py::object env, bool pays, bool keeps_static) {
+          const std::string e = env.is_none() ? std::string() : env.cast<std::string>();
+          return resolve_work(work, env.is_none() ? nullptr : e.c_str(), pays, keeps_static);
+        },
+        py::arg("work"), py::arg("env") = py::none(), py::arg("pays") = false,
+        py::arg("keeps_static") = false);
+  m.def("riemann_queue_pays",
+        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div) {
+          return riemann_queue_pays(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1),
+                                    dtype, div);
         });
   m.attr("TRIG_SERIES_MAX_N") = kTrigSeriesMaxN;
   m.attr("FAST_TRIG_MAX_N") = kFastTrigMaxN;

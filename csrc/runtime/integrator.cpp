@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -106,6 +107,29 @@ RiemannPlan::RiemannPlan(const RiemannConfig& cfg, int device, const Comm* comm)
     multistep_ = resident > 0 && shape_.grid <= resident;
     if (!multistep_) close_launch_ = false;
   }
+  // How the kernel-closed multi-step batches deal their work (RiemannConfig::work).
+  {
+    const std::string w =
+        resolve_work(cfg.work, std::getenv("MIINT_MS_WORK"),
+                     multistep_ && riemann_queue_pays(params_, cfg.dtype, cfg.div),
+                     !multistep_ || close_launch_);
+    MIINT_CHECK(cfg.queue_wg_per_cu >= 0, "queue_wg_per_cu must be >= 0");
+    // one CU's residency (asked only of plans that run the queue)
+    const int per_cu_max =
+        w == "queue" ? riemann_queue_grid(params_, cfg.dtype, cfg.div, cfg.block, 1) : 0;
+    if (per_cu_max > 0) {
+      const int per_cu =
+          cfg.queue_wg_per_cu > 0 ? std::min(cfg.queue_wg_per_cu, per_cu_max) : per_cu_max;
+      // One P for every launch of the plan, never above the items of a FULL batch (a small
+      // virtual grid would otherwise launch a device full of workgroups for a few items). A
+      // shorter batch of the plan still launches P: the pullers beyond its items claim, fail
+      // and leave.
+      const uint64_t items = static_cast<uint64_t>(shape_.grid) * static_cast<uint64_t>(cfg.slots);
+      queue_wgs_ = static_cast<int>(
+          std::min<uint64_t>(static_cast<uint64_t>(per_cu) * info.num_cus, items));
+      work_queue_ = true;
+    }
+  }
 
   // chained batches: two partial halves per step stream
   const int lanes = step_streams(cfg.slots);
@@ -122,6 +146,10 @@ RiemannPlan::RiemannPlan(const RiemannConfig& cfg, int device, const Comm* comm)
   if (close_launch_) {
     ms_ticket_ = DeviceBuffer<unsigned int>(kTicketWords);
     MIINT_HIP(hipMemset(ms_ticket_.get(), 0, ms_ticket_.bytes()));
+  }
+  if (work_queue_) {
+    queue_ = DeviceBuffer<unsigned int>(kQueueWords);
+    MIINT_HIP(hipMemset(queue_.get(), 0, queue_.bytes()));
   }
   result_ = DeviceBuffer<double>(static_cast<size_t>(cfg.slots));
   sync_ = DeviceBuffer<double>(1);
@@ -319,10 +347,7 @@ void RiemannPlan::enqueue_batch(hipStream_t cs, hipStream_t rs, int nsteps, bool
                            static_cast<int>(cfg_.table.size()), slots_.get(), ticket_.get(),
                            scale_, result_ptr(0), cs);
     else if (multistep_)
-      launch_riemann_multistep(params_, cfg_.dtype, cfg_.div, shape_, table_.get(),
-                               static_cast<int>(cfg_.table.size()), ms_partials_.get(), nsteps,
-                               scale_, result_ptr(0), cs,
-                               close_launch_ ? ms_ticket_.get() : nullptr);
+      enqueue_multistep(cs, nsteps, true);
     else
       enqueue_chain_streams(cs, nsteps);
     if (bucketed()) {  // one all-reduce of all the batch's results
@@ -356,6 +381,28 @@ void RiemannPlan::enqueue_batch(hipStream_t cs, hipStream_t rs, int nsteps, bool
   }
   ev_join_.record(rs);
   MIINT_HIP(hipStreamWaitEvent(cs, ev_join_.get(), 0));
+}
+
+// A multi-step batch's persistent launch, static or dealt from the queue (and its closing
+// kernel, unless the launch closes itself or the caller does).
+void RiemannPlan::enqueue_multistep(hipStream_t s, int nsteps, bool close_kernel) const {
+  const int tn = static_cast<int>(cfg_.table.size());
+  if (work_queue_)
+    launch_riemann_queue(params_, cfg_.dtype, cfg_.div, shape_, queue_wgs_, table_.get(), tn,
+                         ms_partials_.get(), nsteps, scale_, result_ptr(0), s, queue_.get(),
+                         close_kernel);
+  else
+    launch_riemann_multistep(params_, cfg_.dtype, cfg_.div, shape_, table_.get(), tn,
+                             ms_partials_.get(), nsteps, scale_, result_ptr(0), s,
+                             close_launch_ ? ms_ticket_.get() : nullptr, close_kernel);
+}
+
+// The queue words of a launch that failed or was abandoned are undefined: zero them (the
+// device may be beyond help; errors here are not reported over the one being thrown).
+void RiemannPlan::reset_queue() const {
+  if (queue_.size() == 0) return;
+  (void)hipSetDevice(device_);
+  (void)hipMemset(queue_.get(), 0, queue_.bytes());
 }
 
 void RiemannPlan::capture_graphs() { batch_graph(cfg_.slots); }
@@ -470,13 +517,18 @@ void RiemannPlan::launch_steps(int steps, bool pipeline, bool graphs) {
 void RiemannPlan::sync() const {
   DeviceGuard g(device_);
   TraceRange tr("miint.plan.sync");
-  if (collective() && cfg_.timeout_s > 0) {  // watchdog: a dead peer must not hang us forever
-    wait_with_timeout(comm_stream_.get(), cfg_.timeout_s, comm_);
-    wait_with_timeout(compute_.get(), cfg_.timeout_s, comm_);
-    return;
+  try {
+    if (collective() && cfg_.timeout_s > 0) {  // watchdog: a dead peer must not hang us forever
+      wait_with_timeout(comm_stream_.get(), cfg_.timeout_s, comm_);
+      wait_with_timeout(compute_.get(), cfg_.timeout_s, comm_);
+      return;
+    }
+    compute_.sync();
+    comm_stream_.sync();
+  } catch (...) {
+    reset_queue();
+    throw;
   }
-  compute_.sync();
-  comm_stream_.sync();
 }
 
 void RiemannPlan::barrier() {
@@ -512,7 +564,6 @@ BatchDiag RiemannPlan::diagnose_batch(int nsteps) {
   TraceRange tr("miint.plan.diagnose_batch");
   check_allreduce_to_host();
   hipStream_t cs = compute_.get();
-  const int tn = static_cast<int>(cfg_.table.size());
   BatchDiag d;
   d.steps = nsteps;
   // pass 1: the batch exactly as launch_steps enqueues it, between two events
@@ -534,9 +585,7 @@ BatchDiag RiemannPlan::diagnose_batch(int nsteps) {
   barrier();
   e0.record(cs);
   if (chained() && nsteps > 1 && multistep_) {
-    launch_riemann_multistep(params_, cfg_.dtype, cfg_.div, shape_, table_.get(), tn,
-                             ms_partials_.get(), nsteps, scale_, result_ptr(0), cs,
-                             close_launch_ ? ms_ticket_.get() : nullptr, false);
+    enqueue_multistep(cs, nsteps, false);
     e1.record(cs);
     if (!close_launch_)
       launch_multistep_close(ms_partials_.get(), shape_.grid, nsteps, scale_, result_ptr(0),
@@ -587,7 +636,7 @@ BatchDiag RiemannPlan::diagnose_batch(int nsteps) {
   return d;
 }
 
-BatchTimeline RiemannPlan::timeline_batch(int nsteps) {
+BatchTimeline RiemannPlan::timeline_batch(int nsteps, const std::string& form) {
   MIINT_CHECK(nsteps >= 1 && nsteps <= cfg_.slots, "timeline_batch: 1 <= steps <= slots");
   MIINT_CHECK(multistep(), "timeline_batch: not a multi-step plan (its batches run chained or "
                            "fused launches: there is no persistent launch to time)");
@@ -595,6 +644,79 @@ BatchTimeline RiemannPlan::timeline_batch(int nsteps) {
   DeviceGuard g(device_);
   TraceRange tr("miint.plan.timeline_batch");
   const DeviceInfo info = device_info(device_);
+  MIINT_CHECK(form == "auto" || form == "static" || form == "queue",
+              "timeline_batch: form must be auto, static or queue (got " + form + ")");
+  MIINT_CHECK(form != "queue" || work_queue_,
+              "timeline_batch: not a queue plan (RiemannConfig::work)");
+  // "auto": the queue's record where the plan was built with work = "queue"; a plan whose
+  // work was left to "auto" records the static launch (the form every earlier record and
+  // reader describes; the same partials and values), unless `form` asks for the queue's
+  if (form == "queue" || (form == "auto" && work_queue_ && cfg_.work == "queue")) {
+    // the queue form: any number of physical workgroups is one launch's timeline (late
+    // ones claim, fail and leave), so there is no residency to refuse
+    BatchTimeline t;
+    t.steps = nsteps;
+    t.grid = shape_.grid;
+    t.block = shape_.block;
+    t.work = "queue";
+    t.workgroups = queue_wgs_;
+    MIINT_HIP(hipDeviceGetAttribute(&t.clock_khz, hipDeviceAttributeWallClockRate, device_));
+    MIINT_CHECK(t.clock_khz > 0, "timeline_batch: the device reports no wall clock rate");
+    const size_t wgs = static_cast<size_t>(queue_wgs_);
+    const size_t items = static_cast<size_t>(shape_.grid) * static_cast<size_t>(nsteps);
+    if (qtl_item_stamp_.size() == 0) {
+      const size_t cap = static_cast<size_t>(shape_.grid) * static_cast<size_t>(cfg_.slots);
+      qtl_item_stamp_ = DeviceBuffer<uint64_t>(cap);
+      qtl_item_owner_ = DeviceBuffer<uint32_t>(cap);
+      qtl_wg_stamps_ = DeviceBuffer<uint64_t>(wgs * 2);
+      qtl_shader_ = DeviceBuffer<uint64_t>(wgs * 2);
+      qtl_hw_ = DeviceBuffer<uint32_t>(wgs * 2);
+    }
+    check_allreduce_to_host();
+    hipStream_t cs = compute_.get();
+    sync();
+    barrier();
+    // sentinels: a cell no workgroup wrote stays kTimelineUnsetStamp / kTimelineUnsetId
+    MIINT_HIP(hipMemsetAsync(qtl_item_stamp_.get(), 0, qtl_item_stamp_.bytes(), cs));
+    MIINT_HIP(hipMemsetAsync(qtl_item_owner_.get(), 0xff, qtl_item_owner_.bytes(), cs));
+    MIINT_HIP(hipMemsetAsync(qtl_wg_stamps_.get(), 0, qtl_wg_stamps_.bytes(), cs));
+    MIINT_HIP(hipMemsetAsync(qtl_shader_.get(), 0, qtl_shader_.bytes(), cs));
+    MIINT_HIP(hipMemsetAsync(qtl_hw_.get(), 0xff, qtl_hw_.bytes(), cs));
+    const QueueTimeline q{qtl_item_stamp_.get(), qtl_item_owner_.get(), qtl_wg_stamps_.get(),
+                          qtl_shader_.get(), qtl_hw_.get()};
+    Event a0, a1;
+    a0.record(cs);
+    launch_riemann_queue(params_, cfg_.dtype, cfg_.div, shape_, queue_wgs_, table_.get(),
+                         static_cast<int>(cfg_.table.size()), ms_partials_.get(), nsteps, scale_,
+                         result_ptr(0), cs, queue_.get(), true, &q);
+    a1.record(cs);
+    if (bucketed())
+      enqueue_bucket_reduce(cs, nsteps);
+    else if (!direct_)
+      MIINT_HIP(hipMemcpyAsync(host_.get(), result_.get(), sizeof(double) * nsteps,
+                               hipMemcpyDeviceToHost, cs));
+    t.item_stamp.resize(items);
+    t.item_owner.resize(items);
+    t.wg_stamps.resize(wgs * 2);
+    t.shader_clock.resize(wgs * 2);
+    t.hw.resize(wgs * 2);
+    MIINT_HIP(hipMemcpyAsync(t.item_stamp.data(), qtl_item_stamp_.get(), items * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, cs));
+    MIINT_HIP(hipMemcpyAsync(t.item_owner.data(), qtl_item_owner_.get(), items * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, cs));
+    MIINT_HIP(hipMemcpyAsync(t.wg_stamps.data(), qtl_wg_stamps_.get(), qtl_wg_stamps_.bytes(),
+                             hipMemcpyDeviceToHost, cs));
+    MIINT_HIP(hipMemcpyAsync(t.shader_clock.data(), qtl_shader_.get(), qtl_shader_.bytes(),
+                             hipMemcpyDeviceToHost, cs));
+    MIINT_HIP(hipMemcpyAsync(t.hw.data(), qtl_hw_.get(), qtl_hw_.bytes(), hipMemcpyDeviceToHost,
+                             cs));
+    sync();
+    last_mode_ = 1;
+    t.device_us = Event::elapsed_ms(a0, a1) * 1e3;
+    t.values.resize(static_cast<size_t>(nsteps));
+    for (int j = 0; j < nsteps; ++j) t.values[static_cast<size_t>(j)] = host_[j];
+    return t;
+  }
   const int resident =
       riemann_timeline_grid(params_, cfg_.dtype, cfg_.div, shape_.block, info.num_cus);
   MIINT_CHECK(shape_.grid <= resident,

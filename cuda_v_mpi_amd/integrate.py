@@ -72,7 +72,8 @@ class Integrator:
                  chain: bool = True, comm_obj=None, threads: int = 0,
                  slice_of: tuple[int, int] | None = None, step_streams: int = 0,
                  block: int = 256, multistep: bool = True, close: str = "auto",
-                 allreduce_to_host: bool = True, timeout_s: float = 300.0, **spec_kw):
+                 allreduce_to_host: bool = True, timeout_s: float = 300.0,
+                 work: str = "auto", queue_wg_per_cu: int = 0, **spec_kw):
         spec = integrands.get(integrand, **spec_kw) if isinstance(integrand, str) else integrand
         if a is not None or b is not None:
             spec = dataclasses.replace(spec, a=spec.a if a is None else a,
@@ -117,6 +118,10 @@ class Integrator:
             cfg.step_streams = step_streams
             cfg.multistep = multistep  # graph batches as one persistent launch
             cfg.close = close  # multi-step batches closed by a kernel or inside the launch
+            if work not in ("auto", "static", "queue"):
+                raise ValueError("work must be auto|static|queue")
+            cfg.work = work  # multi-step batches dealt statically or from a work queue
+            cfg.queue_wg_per_cu = queue_wg_per_cu  # its pullers per CU (0: the residency)
             cfg.allreduce_to_host = allreduce_to_host  # bucketed all-reduce into pinned memory
             cfg.timeout_s = timeout_s  # collective watchdog of the plan's sync (<= 0: none)
             if slice_of is not None:  # (rank, world): that rank's share, on this device
@@ -215,16 +220,21 @@ class Integrator:
         if self._plan is not None:
             self._plan.sync()
 
-    def timeline(self, steps: int) -> dict:
+    def timeline(self, steps: int, form: str = "auto") -> dict:
         """One multi-step batch from the timeline build of its persistent launch
         (``RiemannPlan::timeline_batch``): per workgroup, device-clock stamps at kernel entry,
         after every step's block sum and at exit (``stamps`` uint64 [grid, steps + 2], ticks of
         ``clock_khz``), the shader clock at entry and exit, and the raw XCC_ID / HW_ID words
         (``hw``); ``xcc`` is the XCC id decoded from them. A diagnostic, never timed: read its
-        shares (``tools/timeline_report.py``), not its length."""
+        shares (``tools/timeline_report.py``), not its length.
+
+        A plan built with ``work="queue"`` (or ``form="queue"`` on any plan that runs the
+        queue) records the queue launch instead (``t["work"] == "queue"``): per physical
+        workgroup ``wg_stamps`` [workgroups, 2], per item ``item_stamp`` and ``item_owner``
+        [steps, grid]; ``shader_clock``, ``hw`` and ``xcc`` are per physical workgroup."""
         if self._plan is None:
             raise RuntimeError("timeline needs backend='hip'")
-        t = self._plan.timeline_batch(steps)
+        t = self._plan.timeline_batch(steps, form)
         t["xcc"] = t["hw"][:, 0] & 0xF
         return t
 

@@ -41,6 +41,8 @@ VALU_SLACK = 1.03
 # name -> (kernel file, symbol regex, samples per hot-loop iteration or 0 = not one tile)
 CH = r"riemann_chained_kernel(?:_o8)?ILNS_7DivModeE"
 MS = r"riemann_multistep_kernel(?:_o8)?ILNS_7DivModeE"
+QK = r"riemann_queue_kernel(?:_o8)?ILNS_7DivModeE"
+QT = r"riemann_queue_timeline_kernel(?:_o8)?ILNS_7DivModeE"
 GUARDED = {
     "pi4_series": ("riemann", CH + r"0ENS_3Pi4EE", 384),
     "pi4_ieee": ("riemann", CH + r"1ENS_3Pi4EE", 32),
@@ -67,6 +69,16 @@ GUARDED = {
     # the same step loops with the in-launch close after them (RiemannConfig::close "launch")
     "msc_pi4_series_exact": ("riemann", MS + r"3ENS_3Pi4ELb1EE", 0),
     "msc_pi4_series": ("riemann", MS + r"0ENS_3Pi4ELb1EE", 0),
+    # the same step loops dealt from the work queue (RiemannConfig::work "queue"): the tile
+    # block must keep the multi-step kernel's counts, the claim costs a handful of SALU / VALU
+    # per item outside it; qt_*: the queue's timeline build, at the plain kernel's occupancy
+    "q_pi4_series_exact": ("riemann", QK + r"3ENS_3Pi4EEEv", 0),
+    "q_pi4_series": ("riemann", QK + r"0ENS_3Pi4EEEv", 0),
+    "q_pi4f32_series": ("riemann", QK + r"0ENS0_6Pi4F32EEEv", 0),
+    "q_sin_series": ("riemann", QK + r"0ENS_3SinEEEv", 0),
+    "q_table_series": ("riemann", QK + r"0ENS_5TableEEEv", 0),
+    "q_table_ieee": ("riemann", QK + r"1ENS_5TableEEEv", 0),
+    "qt_pi4_series_exact": ("riemann", QT + r"3ENS_3Pi4EEEv", 0),
     "table2d_stream_0_16": ("table", r"table2d_stream_kernelILi0ELi16ELb0EE", 0),
     "table2d_stream_0_30": ("table", r"table2d_stream_kernelILi0ELi30ELb0EE", 0),
     "table2d_stream_1_16": ("table", r"table2d_stream_kernelILi1ELi16ELb0EE", 0),
