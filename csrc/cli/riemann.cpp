@@ -28,6 +28,9 @@
 // row of numbers per line) or --linspace p0=LO:HI:COUNT the expression may also mention
 // p0..p7 and every row is integrated in one launch (ExprSweep): one line per row (index,
 // parameters, value), or with --json one record carrying rows, nparams and values.
+// With --running the expression's running integral is written as a curve (ExprScan): F at
+// every sample, or every --every K-th one, to --running-out FILE (raw fp64) or as "x value"
+// lines; one rank.
 //
 //   ./riemann [--n 1e9] [--gpus G] [--integrand sin|pi4|poly|train] [--rule left|mid|right]
 //             [--dtype fp64|fp32|fp32acc] [--iters K] [--block 64..1024] [--grid G] [--parity]
@@ -280,8 +283,77 @@ int run_expr_sweep(const cli::Args& a, const RiemannConfig& cfg, double nd, int 
   return 0;
 }
 
+// --expr --running: the running integral F_i = h * sum_{j <= i} f(x_j) as a curve (ExprScan),
+// every --every K-th value of it. One rank. The values go to --running-out FILE as raw
+// little-endian fp64, or to stdout as "x value" lines (at most kRunningMaxLines of them).
+constexpr uint64_t kRunningMaxLines = 10000;
+
+int run_expr_running(const cli::Args& a, const RiemannConfig& cfg, double nd) {
+  MIINT_CHECK(!a.has("params") && !a.has("linspace"),
+              "--running integrates one expression (no --params / --linspace)");
+  MIINT_CHECK(!cli::on_cpu(a), "--running has no host engine (--device cpu): it runs on the GPU");
+  MIINT_CHECK(!a.has("gpus") && !a.has("loopback") && cli::env_int("WORLD_SIZE", 1) == 1,
+              "--running is a one-rank program: no --gpus, --loopback or rank environment "
+              "(WORLD_SIZE); slices and rank carries are ExprScan's, through its communicator");
+  const std::string expr = a.str("expr", "");
+  const long long ev = a.integer("every", 1);
+  MIINT_CHECK(ev >= 1, "--every must be >= 1");
+  const uint64_t every = static_cast<uint64_t>(ev);
+  MIINT_CHECK(cfg.n >= 1, "--running needs --n >= 1");
+  const uint64_t outputs = expr_scan_outputs(0, cfg.n, every);
+  const std::string path = a.str("running-out", "");
+  MIINT_CHECK(!path.empty() || outputs <= kRunningMaxLines,
+              "--running would print " + std::to_string(outputs) + " lines (more than " +
+                  std::to_string(kRunningMaxLines) + "): thin them with --every K or write raw "
+                  "fp64 values with --running-out FILE");
+  expr_scan_check(cfg.n, 0, cfg.n, every, outputs);
+  MIINT_CHECK(device_count() >= 1, "--running needs a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprScan scan(expr, 0);
+  DeviceBuffer<double> out(std::max<uint64_t>(outputs, 1));
+  const ExprScanResult r =
+      scan.run(cfg.a, cfg.b, cfg.n, cfg.rule, 0, cfg.n, every, out.get(), outputs);
+  const double h = (cfg.b - cfg.a) / static_cast<double>(cfg.n);
+  const uint64_t chunk = 1ull << 22;  // values copied to the host at a time
+  std::vector<double> host(std::min<uint64_t>(std::max<uint64_t>(outputs, 1), chunk));
+  std::FILE* f = nullptr;
+  if (!path.empty()) {
+    f = std::fopen(path.c_str(), "wb");
+    MIINT_CHECK(f != nullptr, "--running-out: cannot open " + path + " for writing");
+  }
+  for (uint64_t j0 = 0; j0 < outputs; j0 += chunk) {
+    const uint64_t m = std::min<uint64_t>(chunk, outputs - j0);
+    MIINT_HIP(hipMemcpy(host.data(), out.get() + j0, m * sizeof(double), hipMemcpyDeviceToHost));
+    if (f) {
+      if (std::fwrite(host.data(), sizeof(double), m, f) != m) {
+        std::fclose(f);
+        fail("--running-out: short write to " + path, __FILE__, __LINE__);
+      }
+    } else {
+      for (uint64_t j = 0; j < m; ++j)  // x: the upper limit the value belongs to
+        std::printf("%.17g %.17g\n",
+                    cfg.a + static_cast<double>(j0 + j + 1) * (static_cast<double>(every) * h),
+                    host[j]);
+    }
+  }
+  if (f) MIINT_CHECK(std::fclose(f) == 0, "--running-out: cannot close " + path);
+  const double secs = wall_seconds() - process_start_seconds();
+  if (f) print_result(secs, cfg.b, nd, r.total);
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b).add("n", nd)
+      .add("rule", a.str("rule", "left")).add("running", true)
+      .add("every", static_cast<double>(every)).add("outputs", static_cast<double>(r.outputs))
+      .add("total", r.total);
+  if (f) rec.add("running_out", path);
+  cli::emit(a, rec.add("device_ms", r.device_ms)
+                   .add("subintervals_per_s", r.device_ms > 0 ? nd / (r.device_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (a.flag("running")) return run_expr_running(a, cfg, nd);
   if (a.has("params") || a.has("linspace")) return run_expr_sweep(a, cfg, nd, iters);
   if (cli::on_cpu(a)) return run_host_expr(a, cfg, nd, iters);
   const std::string expr = a.str("expr", "");
@@ -339,8 +411,13 @@ constexpr const char* kUsage =
     "               [--device cpu [--threads T] [--ranks P]]\n"
     "               [--expr EXPR --a A --b B [--analytic V]]\n"
     "               [--expr EXPR --params FILE | --linspace p0=LO:HI:COUNT]\n"
+    "               [--expr EXPR --a A --b B --n N --running [--every K] [--running-out FILE]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
-    "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n";
+    "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n"
+    "--running: the running integral F(x) = h * sum of f up to x at every sample (one GPU,\n"
+    "  one rank): every K-th value with --every K (global sample index: (i + 1) % K == 0);\n"
+    "  values go to --running-out FILE as raw little-endian fp64, else to stdout as 'x value'\n"
+    "  lines, refused above 10000 lines; --json adds total, outputs, every and device_ms.\n";
 
 int main(int argc, char** argv) {
   try {
@@ -384,6 +461,10 @@ int main(int argc, char** argv) {
 
     MIINT_CHECK(a.has("expr") || !(a.has("params") || a.has("linspace")),
                 "--params / --linspace sweep the parameters of an --expr integrand");
+    MIINT_CHECK(a.has("expr") || !a.has("running"),
+                "--running is the running integral of an --expr integrand");
+    MIINT_CHECK(a.flag("running") || !(a.has("every") || a.has("running-out")),
+                "--every / --running-out belong to --running");
     if (a.has("expr")) return run_expr(a, cfg, nd, iters);
     if (cli::on_cpu(a)) return run_host(a, cfg, nd, iters);
     const cli::Topology topo = cli::topology(a);

@@ -171,4 +171,102 @@ class ExprSweep {
   Event e0_, e1_;
 };
 
+// ---------------------------------------------------------------------------------------
+// Running integrals: F_i = scale * h * sum_{j <= i} f(x_j) at every sample (or every
+// `every`-th one) of a run-time integrand, in one call.
+//
+// The reference's second half (4main.c) integrates a profile to a curve; TrainScan does
+// that for the velocity table. Here the integrand is any expression over x: the distance
+// curve of a user's v(t), a CDF, an error function. Reduce-then-scan on the computed
+// samples, three stream-ordered kernels around the expression (expr_scan.cpp):
+//
+//   miint_expr_scan_tile_sums    tiles of 4096 samples (256 threads x 16 consecutive ones);
+//                                a workgroup walks a contiguous run of R tiles: per tile the
+//                                sum S (compute only) -> L[t], the sum of the run's tiles
+//                                before t, and A[b], the run's sum. At most 2048 runs: one
+//                                workgroup per tile (244 141 of them at 1e9 samples) ran at
+//                                the dispatch rate, 2.2x the time of an ExprIntegrator pass
+//   miint_expr_scan_tile_prefix  one workgroup, a contiguous stretch of (at most two) runs
+//                                per thread -> exclusive B[b] and the slice sum T;
+//                                P[t] = B[t / R] + L[t] is tile t's exclusive prefix
+//   (world > 1)                  allgather of one T per rank, launch_exclusive_carry -> C
+//   miint_expr_scan_write        re-evaluates a tile, scans it and stores
+//                                ((C + P[t]) + local) * (h * scale); every == 1: 16-byte
+//                                stores through an LDS transpose; every > 1: 8-byte stores of
+//                                the selected samples, tiles without one are not evaluated
+//
+// No workgroup waits on another (no tickets, no look-back, no timeout path): nothing depends
+// on co-residency. The launch shape depends on `count` (and `every`) only and every sum has
+// a fixed order, so results are bitwise reproducible. Sample i sits at
+// x = fma((double)i + off, h, a), the bits ExprIntegrator gives it. Samples, tiles and output
+// positions are 64-bit.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t EXPR_SCAN_TILE = 4096;            // 256 threads x 16 samples
+constexpr uint64_t kExprScanMaxRuns = 2048;          // workgroups of the sums and write passes
+constexpr uint64_t kExprScanMaxTiles = 1ull << 22;   // tiles of one launch (L: 32 MB)
+
+// Kernel source / code object of the scan kernels for `expr` (as expr_source / expr_compile).
+std::string expr_scan_source(const std::string& expr);
+std::string expr_scan_compile(const std::string& expr);
+struct ScanShape {
+  uint64_t tiles = 0, run = 1, runs = 0;
+};
+// How a slice of `count` samples is dealt out (no device needed): tiles = ceil(count / 4096),
+// run = R = max(ceil(tiles / 2048), 1) tiles per workgroup, runs = ceil(tiles / R). Throws
+// past kExprScanMaxTiles tiles.
+ScanShape expr_scan_shape(uint64_t count);
+// Values a launch over samples [begin, begin + count) writes: those F_i with
+// (i + 1) % every == 0, i the global sample index: floor((begin + count) / every) -
+// floor(begin / every). No device needed.
+uint64_t expr_scan_outputs(uint64_t begin, uint64_t count, uint64_t every);
+// Throws, naming the numbers, unless [begin, begin + count) lies in [0, n) without wrapping,
+// every >= 1, out_capacity holds the launch's outputs and the slice has at most
+// kExprScanMaxTiles tiles. No device needed; nothing is launched after a refusal.
+void expr_scan_check(uint64_t n, uint64_t begin, uint64_t count, uint64_t every,
+                     uint64_t out_capacity);
+
+struct ExprScanResult {
+  double total = 0.0;      // scale * h * sum over the launch, or over all ranks' slices
+  uint64_t outputs = 0;    // values written to out_device
+  double device_ms = 0.0;  // events around the launch's kernels (and collectives)
+};
+
+class ExprScan {
+ public:
+  ExprScan(const std::string& expr, int device = 0);
+  ~ExprScan();
+  ExprScan(const ExprScan&) = delete;
+  ExprScan& operator=(const ExprScan&) = delete;
+  // Writes F_i = scale * h * sum_{begin <= j <= i} f(x_j) for the selected samples of
+  // [begin, begin + count) to out_device (device memory, out_capacity doubles), in order.
+  // With a communicator of more than one rank the ranks hold consecutive slices in rank
+  // order, rank r's values carry the lower ranks' slice sums (added in rank order) and
+  // `total` is the sum over all slices, the same double on every rank. Synchronous.
+  ExprScanResult run(double a, double b, uint64_t n, Rule rule, uint64_t begin, uint64_t count,
+                     uint64_t every, double* out_device, uint64_t out_capacity,
+                     double scale = 1.0, const Comm* comm = nullptr);
+  // Device ms per scan over `iters` back-to-back scans (events, no host sync between them).
+  double time(double a, double b, uint64_t n, Rule rule, uint64_t begin, uint64_t count,
+              uint64_t every, double* out_device, uint64_t out_capacity, int iters);
+  const std::string& expression() const { return expr_; }
+
+ private:
+  void reserve(uint64_t tiles, int world);
+  void enqueue_local(double a, double h, double off, uint64_t begin, uint64_t count,
+                     hipStream_t s);
+  void enqueue_write(double a, double h, double off, uint64_t begin, uint64_t count,
+                     uint64_t every, const double* carry, double hs, double* out,
+                     hipStream_t s);
+  std::string expr_;
+  int device_;
+  hipModule_t module_ = nullptr;
+  hipFunction_t sums_fn_ = nullptr, prefix_fn_ = nullptr, write_fn_ = nullptr;
+  Stream stream_;
+  DeviceBuffer<double> local_;    // L[t]: grows on demand, kept across calls
+  DeviceBuffer<double> runs_;     // A[b], then B[b]: 2 x kExprScanMaxRuns
+  DeviceBuffer<double> scalars_;  // [0] T, [1] C, [2..) the ranks' gathered T
+  PinnedBuffer<double> host_;           // the ranks' T (one without a communicator)
+  Event e0_, e1_;
+};
+
 }  // namespace miint

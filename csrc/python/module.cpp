@@ -842,6 +842,64 @@ PYBIND11_MODULE(_miint, m) {
       .def_property_readonly("expression", &ExprSweep::expression)
       .def_property_readonly("nparams", &ExprSweep::nparams);
 
+  // running integrals: F_i = scale * h * sum_{j <= i} f(x_j) on the sample grid
+  m.attr("EXPR_SCAN_TILE") = EXPR_SCAN_TILE;
+  m.attr("EXPR_SCAN_MAX_TILES") = kExprScanMaxTiles;
+  m.def("expr_scan_source", &expr_scan_source, py::arg("expr"),
+        "source of the running-integral kernels generated for an expression over x");
+  m.def("expr_scan_compile", [](const std::string& e) {
+          std::string code;
+          {
+            py::gil_scoped_release nogil;
+            code = expr_scan_compile(e);
+          }
+          return py::bytes(code);
+        },
+        py::arg("expr"),
+        "compile the running-integral kernels for gfx950 with hipRTC (no device needed)");
+  m.def("expr_scan_shape", [](uint64_t count) {
+          const ScanShape s = expr_scan_shape(count);
+          return py::make_tuple(s.tiles, s.run, s.runs);
+        },
+        py::arg("count"), "(tiles, tiles per run, runs) of a scan of `count` samples");
+  m.def("expr_scan_outputs", &expr_scan_outputs, py::arg("begin"), py::arg("count"),
+        py::arg("every"), "values a scan of samples [begin, begin + count) writes");
+  m.def("expr_scan_check", &expr_scan_check, py::arg("n"), py::arg("begin"), py::arg("count"),
+        py::arg("every"), py::arg("out_capacity"),
+        "raise unless the slice, `every` and the output capacity are ones a scan accepts");
+  py::class_<ExprScan>(m, "ExprScan",
+                       "running integral of f(x) given as an expression (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("device") = 0)
+      .def("run",
+           [](ExprScan& e, double a, double b, uint64_t n, Rule rule, uint64_t begin,
+              uint64_t count, uint64_t every, uintptr_t out, uint64_t out_capacity, double scale,
+              const Comm* comm) {
+             ExprScanResult r;
+             {
+               py::gil_scoped_release nogil;  // loopback collectives barrier across threads
+               r = e.run(a, b, n, rule, begin, count, every, reinterpret_cast<double*>(out),
+                         out_capacity, scale, comm);
+             }
+             py::dict d;
+             d["total"] = r.total;
+             d["outputs"] = r.outputs;
+             d["device_ms"] = r.device_ms;
+             return d;
+           },
+           py::arg("a"), py::arg("b"), py::arg("n"), py::arg("rule"), py::arg("begin"),
+           py::arg("count"), py::arg("every"), py::arg("out"), py::arg("out_capacity"),
+           py::arg("scale") = 1.0, py::arg("comm") = nullptr)
+      .def("time",
+           [](ExprScan& e, double a, double b, uint64_t n, Rule rule, uint64_t begin,
+              uint64_t count, uint64_t every, uintptr_t out, uint64_t out_capacity, int iters) {
+             return e.time(a, b, n, rule, begin, count, every, reinterpret_cast<double*>(out),
+                           out_capacity, iters);
+           },
+           py::arg("a"), py::arg("b"), py::arg("n"), py::arg("rule"), py::arg("begin"),
+           py::arg("count"), py::arg("every"), py::arg("out"), py::arg("out_capacity"),
+           py::arg("iters"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprScan::expression);
+
   // ------------------------------------------------------------------ host (CPU) engine
   m.def("host_isa", &host_isa, "vector ISA the host kernels dispatch to: avx512|avx2|base");
   py::class_<HostPool>(m, "HostPool", "persistent host worker threads (0 = one per core)")

@@ -16,7 +16,9 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
   * any integrand at run time: one C++ expression over x compiled for gfx950 with hipRTC
     (``ops.kernels.riemann_expr``, ``riemann --expr``), and parameter sweeps of it:
     f(x, p0..p7) over K parameter rows per launch (``integrate_expr_sweep``,
-    ``riemann --expr ... --params FILE``).
+    ``riemann --expr ... --params FILE``), and its running integral as a curve: F(x) at
+    every sample, or every K-th one, in one call (``integrate_expr_running``,
+    ``ops.kernels.riemann_expr_scan``, ``riemann --expr ... --running``).
 
 Layout: models/ (integrands), ops/ (kernel entry points), parallel/ (decomposition,
 process groups), utils/ (fixtures, oracles, output formats), integrate.py (high-level API).
@@ -28,4 +30,5 @@ __version__ = "0.1.0"
 from ._native import native, require_gpu  # noqa: F401
 from .integrate import IntegrationResult, Integrator, integrate, integrate_expr  # noqa: F401
 from .integrate import SweepResult, integrate_expr_sweep  # noqa: F401
+from .integrate import RunningResult, integrate_expr_running  # noqa: F401
 from .models import integrands  # noqa: F401

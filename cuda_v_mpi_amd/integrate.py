@@ -340,3 +340,101 @@ def integrate_expr_sweep(expr: str, params, a: float, b: float, n: int = 10**6,
         err = [abs(v - w) for v, w in zip(values, want)]
     return SweepResult(values=values, abs_err=err, rows=len(values), nparams=int(p.shape[1]),
                        n=int(n), expr=expr, rule=rule, seconds=secs)
+
+
+@dataclasses.dataclass
+class RunningResult:
+    x: torch.Tensor         # upper limits: x[j] = a + (j + 1) * every * h
+    values: torch.Tensor    # values[j] ~ the integral of f from a to x[j] (fp64)
+    total: float            # h * sum over all n samples
+    device_ms: float        # the scan's kernels (hip) or the evaluation (cpu), in ms
+
+
+# What the torch form of an expression may call: the C names of the device math library that
+# torch has under one name or another.
+_TORCH_MATH = {
+    "sin": torch.sin, "cos": torch.cos, "tan": torch.tan, "asin": torch.asin,
+    "acos": torch.acos, "atan": torch.atan, "atan2": torch.atan2, "sinh": torch.sinh,
+    "cosh": torch.cosh, "tanh": torch.tanh, "exp": torch.exp, "exp2": torch.exp2,
+    "expm1": torch.expm1, "log": torch.log, "log2": torch.log2, "log10": torch.log10,
+    "log1p": torch.log1p, "sqrt": torch.sqrt, "rsqrt": torch.rsqrt, "fabs": torch.abs,
+    "abs": torch.abs, "erf": torch.erf, "erfc": torch.erfc, "floor": torch.floor,
+    "ceil": torch.ceil, "pow": torch.pow, "fmin": torch.fmin, "fmax": torch.fmax,
+    "hypot": torch.hypot, "fma": lambda p, q, r: p * q + r,
+}
+
+
+def expr_torch(expr: str, x: torch.Tensor) -> torch.Tensor:
+    """The torch form of a run-time expression: f(x) element-wise in x's dtype, for an
+    expression made of numbers, ``x``, + - * /, parentheses and the math functions torch has
+    (sin, exp, pow, fabs, ...). The syntax tree is walked, nothing is ``eval``-ed; anything
+    else (``?:``, comparisons, other names) raises ValueError: the cpu backend covers the
+    arithmetic subset of what the hipRTC backends compile."""
+    import ast
+
+    try:
+        tree = ast.parse(expr.strip(), mode="eval")
+    except SyntaxError as e:
+        raise ValueError(f"the cpu backend cannot read the expression {expr!r}: {e.msg}") from None
+    binops = {ast.Add: torch.add, ast.Sub: torch.sub, ast.Mult: torch.mul, ast.Div: torch.div}
+
+    def const(v):
+        return torch.tensor(float(v), dtype=x.dtype)
+
+    def walk(node):
+        if isinstance(node, ast.Expression):
+            return walk(node.body)
+        if isinstance(node, ast.Constant) and type(node.value) in (int, float):
+            return const(node.value)
+        if isinstance(node, ast.Name) and node.id == "x":
+            return x
+        if isinstance(node, ast.BinOp) and type(node.op) in binops:
+            return binops[type(node.op)](walk(node.left), walk(node.right))
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
+            v = walk(node.operand)
+            return -v if isinstance(node.op, ast.USub) else v
+        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Name)
+                and node.func.id in _TORCH_MATH and not node.keywords):
+            return _TORCH_MATH[node.func.id](*[walk(arg) for arg in node.args])
+        raise ValueError(f"the cpu backend does not evaluate {ast.dump(node)[:60]} "
+                         f"(expression {expr!r})")
+
+    return walk(tree) + torch.zeros_like(x)  # a constant expression still has x's shape
+
+
+def integrate_expr_running(expr: str, a: float, b: float, n: int, rule: str = "left",
+                           every: int = 1, backend: str = "hip") -> RunningResult:
+    """The running integral of any f(x) given as one C++ expression over ``x``, as a curve:
+    ``values[j] = h * sum of f(x_i) over samples i < (j + 1) * every`` of the n-sample rule on
+    [a, b], which approximates the integral of f from a to ``x[j] = a + (j + 1) * every * h``
+    (floor(n / every) values; every = 1: one per sample). A distance curve from a velocity, a
+    CDF from a density, an error function, an accumulated dose.
+
+    ``backend="hip"``: three hipRTC-compiled gfx950 kernels, only the values are written to
+    HBM (``ops.kernels.riemann_expr_scan``). ``backend="cpu"``: the torch fp64 form, ``cumsum``
+    of the per-sample values at x_i = a + (i + off) * h (``expr_torch``'s subset of
+    expressions); needs no GPU."""
+    if rule not in ("left", "mid", "right"):
+        raise ValueError("rule must be left|mid|right")
+    n, every = int(n), int(every)
+    if n < 1 or every < 1:
+        raise ValueError("integrate_expr_running needs n >= 1 and every >= 1")
+    a, b = float(a), float(b)
+    h = (b - a) / n
+    if backend == "hip":
+        from .ops import kernels
+
+        values, rec = kernels._expr_scan(expr, a, b, n, rule, every, 0, None, None)
+        total, ms = rec["total"], rec["device_ms"]
+    elif backend == "cpu":
+        off = {"left": 0.0, "mid": 0.5, "right": 1.0}[rule]
+        t0 = time.perf_counter()
+        run = torch.cumsum(expr_torch(expr, a + (torch.arange(n, dtype=torch.float64) + off) * h),
+                           dim=0)
+        values = run[every - 1::every] * h
+        total = float(run[-1]) * h
+        ms = (time.perf_counter() - t0) * 1e3
+    else:
+        raise ValueError("integrate_expr_running backend must be 'hip' or 'cpu'")
+    x = a + torch.arange(1, values.numel() + 1, dtype=torch.float64) * (every * h)
+    return RunningResult(x=x.to(values.device), values=values, total=total, device_ms=ms)

@@ -427,3 +427,41 @@ def riemann_expr_sweep(expr: str, params, a: float, b: float, n: int, rule: str 
     vals = es.integrate(p, float(a), float(b), int(n), getattr(m.Rule, rule), int(i_begin),
                         int(n_local))
     return torch.as_tensor(vals, dtype=torch.float64).to(dev)
+
+
+_EXPR_SCAN_CACHE: dict = {}
+
+
+def riemann_expr_scan(expr: str, a: float, b: float, n: int, rule: str = "left", every: int = 1,
+                      i_begin: int = 0, n_local: int | None = None,
+                      out: torch.Tensor | None = None) -> tuple[torch.Tensor, float]:
+    """Running integral of any f(x) given as one C++ expression over ``x``: F_i = h * sum of
+    f(x_j) over samples i_begin <= j <= i of the n-sample rule on [a, b], for every sample i
+    of [i_begin, i_begin + n_local) with (i + 1) % every == 0 (i the global index; every = 1:
+    all of them). Three hipRTC-compiled kernels per expression, cached with their module per
+    (expression, device): tile sums, tile prefix, one write pass (csrc/runtime/expr_scan.cpp);
+    nothing but the written values touches HBM. Returns (a 1-D fp64 device tensor of the
+    written values, the total h * sum over the slice). ``out``: a contiguous fp64 device
+    tensor to write into (at least as many elements as values are written)."""
+    values, r = _expr_scan(expr, a, b, n, rule, every, i_begin, n_local, out)
+    return values, r["total"]
+
+
+def _expr_scan(expr, a, b, n, rule, every, i_begin, n_local, out):
+    """riemann_expr_scan's work: (values, ExprScan.run's record: total, outputs, device_ms)."""
+    m = native()
+    dev = _device()
+    key = (expr, dev.index)
+    es = _EXPR_SCAN_CACHE.get(key)
+    if es is None:
+        es = _EXPR_SCAN_CACHE[key] = m.ExprScan(expr, dev.index)
+    n_local = n - i_begin if n_local is None else n_local
+    count = m.expr_scan_outputs(int(i_begin), int(n_local), int(every))
+    if out is None:
+        out = torch.empty(count, dtype=torch.float64, device=dev)
+    else:
+        _check(out, dtype=torch.float64, name="out")
+    torch.cuda.current_stream(dev).synchronize()  # the scan runs on its own stream
+    r = es.run(float(a), float(b), int(n), getattr(m.Rule, rule), int(i_begin), int(n_local),
+               int(every), out.data_ptr(), out.numel())
+    return out[:count], r
