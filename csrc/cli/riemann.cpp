@@ -30,7 +30,9 @@
 // parameters, value), or with --json one record carrying rows, nparams and values.
 // With --running the expression's running integral is written as a curve (ExprScan): F at
 // every sample, or every --every K-th one, to --running-out FILE (raw fp64) or as "x value"
-// lines; one rank.
+// lines; one rank. With --ya AY --yb BY the expression is over x and y and its double integral
+// on [a, b] x [ya, yb] is taken with --n x --ny samples (ExprIntegrator2D, HostExpr2D), the
+// ranks splitting the sample rows.
 //
 //   ./riemann [--n 1e9] [--gpus G] [--integrand sin|pi4|poly|train] [--rule left|mid|right]
 //             [--dtype fp64|fp32|fp32acc] [--iters K] [--block 64..1024] [--grid G] [--parity]
@@ -351,8 +353,117 @@ int run_expr_running(const cli::Args& a, const RiemannConfig& cfg, double nd) {
   return 0;
 }
 
+// --expr with --ya AY --yb BY: the double integral of f(x, y) on [a, b] x [ya, yb], n x ny
+// samples (--ny, default --n), the same rule on both axes. Ranks split the sample rows.
+struct Rule2D {
+  double ya = 0.0, yb = 0.0, nyd = 0.0;
+  uint64_t ny = 0;
+};
+
+Rule2D rule2d(const cli::Args& a, const RiemannConfig& cfg, double nd) {
+  MIINT_CHECK(!a.flag("running"), "--running is a curve in x: no --ya / --yb double integral");
+  MIINT_CHECK(!a.has("params") && !a.has("linspace"),
+              "--ya / --yb integrate one expression over x and y (no --params / --linspace)");
+  Rule2D r;
+  r.ya = a.num("ya", 0.0);
+  r.yb = a.num("yb", 0.0);
+  r.nyd = a.num("ny", nd);
+  MIINT_CHECK(cfg.n >= 1 && r.nyd >= 1, "--ya / --yb need --n >= 1 and --ny >= 1");
+  r.ny = static_cast<uint64_t>(r.nyd);
+  return r;
+}
+
+void print_result2d(double secs, const RiemannConfig& cfg, const Rule2D& y, double nd,
+                    double result) {
+  std::printf("%lf seconds\n", secs);
+  std::cout.precision(15);
+  std::cout << "The integral of f(x, y) over [" << cfg.a << ", " << cfg.b << "] x [" << y.ya
+            << ", " << y.yb << "] with " << nd << " x " << y.nyd << " steps is " << result
+            << std::endl;
+}
+
+cli::JsonRecord record2d(const cli::Args& a, const RiemannConfig& cfg, const Rule2D& y,
+                         double nd, double result) {
+  cli::JsonRecord r;
+  r.add("program", "riemann").add("expr", a.str("expr", "")).add("a", cfg.a).add("b", cfg.b)
+      .add("ya", y.ya).add("yb", y.yb).add("n", nd).add("ny", y.nyd)
+      .add("rule", a.str("rule", "left")).add("value", result);
+  if (a.has("analytic")) {
+    const double exact = a.num("analytic", 0.0);
+    r.add("analytic", exact).add("abs_err", std::fabs(result - exact));
+  }
+  return r;
+}
+
+int run_host_expr2d(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  const Rule2D y = rule2d(a, cfg, nd);
+  cli::HostRanks hr = cli::host_ranks(a);
+  HostPool pool(hr.threads);
+  const HostExpr2D he(a.str("expr", ""));
+  uint64_t b = 0, c = 0;
+  rank_slice(y.ny, hr.rank, hr.world, &b, &c);
+  double result = 0.0, host_ms = 0.0;
+  for (int i = 0; i < iters; ++i) {  // best of --iters
+    if (hr.comm) hr.comm->barrier();
+    const double t0 = wall_seconds();
+    double v = he.integrate(cfg.a, cfg.b, cfg.n, y.ya, y.yb, y.ny, cfg.rule, b, c, pool);
+    if (hr.comm) hr.comm->allreduce_sum(&v, 1);
+    const double ms = (wall_seconds() - t0) * 1e3;
+    if (i == 0 || ms < host_ms) host_ms = ms;
+    result = v;
+  }
+  if (hr.rank != 0) return 0;
+  const double secs = wall_seconds() - process_start_seconds();
+  print_result2d(secs, cfg, y, nd, result);
+  cli::emit(a, record2d(a, cfg, y, nd, result)
+                   .add("device", "cpu").add("ranks", hr.world)
+                   .add("threads_per_rank", pool.threads()).add("host_ms", host_ms)
+                   .add("samples_per_s", host_ms > 0 ? nd * y.nyd / (host_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
+int run_expr2d(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (cli::on_cpu(a)) return run_host_expr2d(a, cfg, nd, iters);
+  const Rule2D y = rule2d(a, cfg, nd);
+  const std::string expr = a.str("expr", "");
+  const cli::Topology topo = cli::topology(a);
+  double result = 0.0, dev_ms = 0.0;
+  std::mutex mu;
+  cli::RankFacts facts;
+  cli::run_ranks(topo, [&](int rank, int dev, const Comm* comm) {
+    ExprIntegrator2D ei(expr, dev, cfg.grid);
+    RankAgree agree(comm);
+    uint64_t b = 0, c = 0;
+    rank_slice(y.ny, rank, topo.world, &b, &c);
+    const double v =
+        ei.integrate(cfg.a, cfg.b, cfg.n, y.ya, y.yb, y.ny, cfg.rule, b, c, 1.0, comm);
+    // barrier right before the clock starts; the slowest rank's time
+    const double ms = agree.max(ei.time(cfg.a, cfg.b, cfg.n, y.ya, y.yb, y.ny, cfg.rule, b, c,
+                                        iters, [&] { agree.barrier(); },
+                                        [&] { fault::delay(rank); }));
+    std::lock_guard<std::mutex> g(mu);
+    if (rank == topo.rank0) {
+      result = v;
+      dev_ms = ms;
+      facts.note(comm);
+    }
+  });
+  if (topo.rank0 != 0) return 0;
+  const double secs = wall_seconds() - process_start_seconds();
+  print_result2d(secs, cfg, y, nd, result);
+  cli::JsonRecord r = record2d(a, cfg, y, nd, result);
+  r.add("gpus", topo.world);
+  facts.add(r, topo);
+  cli::emit(a, r.add("device_ms", dev_ms)
+                   .add("samples_per_s", dev_ms > 0 ? nd * y.nyd / (dev_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (a.has("ya")) return run_expr2d(a, cfg, nd, iters);
   if (a.flag("running")) return run_expr_running(a, cfg, nd);
   if (a.has("params") || a.has("linspace")) return run_expr_sweep(a, cfg, nd, iters);
   if (cli::on_cpu(a)) return run_host_expr(a, cfg, nd, iters);
@@ -412,12 +523,17 @@ constexpr const char* kUsage =
     "               [--expr EXPR --a A --b B [--analytic V]]\n"
     "               [--expr EXPR --params FILE | --linspace p0=LO:HI:COUNT]\n"
     "               [--expr EXPR --a A --b B --n N --running [--every K] [--running-out FILE]]\n"
+    "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
     "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n"
     "--running: the running integral F(x) = h * sum of f up to x at every sample (one GPU,\n"
     "  one rank): every K-th value with --every K (global sample index: (i + 1) % K == 0);\n"
     "  values go to --running-out FILE as raw little-endian fp64, else to stdout as 'x value'\n"
-    "  lines, refused above 10000 lines; --json adds total, outputs, every and device_ms.\n";
+    "  lines, refused above 10000 lines; --json adds total, outputs, every and device_ms.\n"
+    "--ya AY --yb BY: the double integral of --expr over x and y on [AX, BX] x [AY, BY], NX x NY\n"
+    "  samples (--ny defaults to --n), the same rule on both axes; ranks split the sample rows\n"
+    "  (--gpus, --loopback, rank environment, --device cpu [--threads T] as for --expr);\n"
+    "  --json: expr, a, b, ya, yb, n, ny, rule, value, device_ms, samples_per_s.\n";
 
 int main(int argc, char** argv) {
   try {
@@ -465,6 +581,12 @@ int main(int argc, char** argv) {
                 "--running is the running integral of an --expr integrand");
     MIINT_CHECK(a.flag("running") || !(a.has("every") || a.has("running-out")),
                 "--every / --running-out belong to --running");
+    MIINT_CHECK(a.has("ya") == a.has("yb"),
+                "--ya and --yb go together: the y interval of a double integral");
+    MIINT_CHECK(a.has("ya") || !a.has("ny"),
+                "--ny belongs to a double integral (--ya AY --yb BY)");
+    MIINT_CHECK(a.has("expr") || !a.has("ya"),
+                "--ya / --yb are the double integral of an --expr integrand over x and y");
     if (a.has("expr")) return run_expr(a, cfg, nd, iters);
     if (cli::on_cpu(a)) return run_host(a, cfg, nd, iters);
     const cli::Topology topo = cli::topology(a);

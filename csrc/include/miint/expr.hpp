@@ -269,4 +269,100 @@ class ExprScan {
   Event e0_, e1_;
 };
 
+// ---------------------------------------------------------------------------------------
+// Double integrals: sum of f(x, y) over the nx x ny samples of a rectangle [ax, bx] x [ay, by]
+// (the same rule on both axes), for one C++ expression over x and y.
+//
+// Through ExprSweep a double integral is f(x, p0) with one parameter row per y sample: at
+// most 2^20 rows, the y values uploaded as data, every x coordinate formed again for every
+// row, gx partials written and closed per row. Here a lane keeps a few columns in registers
+// and runs down a contiguous stretch of rows (expr2d.cpp):
+//
+//   miint_expr2d_partials  256 lanes = lx along x by 256 / lx along y. An item is a column
+//                          panel (lx * cpl columns, cpl <= 4 per lane) by a row stretch. A
+//                          lane forms its columns' x once per item, then per row y once and
+//                          per sample f and one add (cpl accumulators); what f does with x
+//                          alone is hoisted out of the row loop by the compiler. A workgroup
+//                          takes a contiguous run of items; wave64 butterfly + 4-wave LDS sum
+//                          -> one partial per workgroup
+//   miint_expr2d_finalize  one workgroup sums the partials in index order
+//                          -> ((hx * hy) * scale) * sum
+//
+// Sample (i, j) sits at x_i = fma((double)i + off, hx, ax), y_j = fma((double)j + off, hy, ay):
+// the bits ExprIntegrator gives a coordinate. A launch covers all nx columns of rows
+// [row_begin, row_begin + row_count); ranks split the rows (rank_slice(ny, r, world)). The
+// launch shape depends on (nx, row_count, grid) only and every sum has a fixed order:
+// bitwise reproducible. No workgroup waits on another. Rows and flattened samples are 64-bit.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t kExpr2DMaxNx = (1ull << 32) - 1;
+constexpr uint64_t kExpr2DMaxNy = 1ull << 40;
+constexpr int kExpr2DMaxGrid = 2048;
+
+std::string expr2d_source(const std::string& expr);
+// hipRTC compile for gfx950 (no device needed), cached per expression.
+std::string expr2d_compile(const std::string& expr);
+
+struct Expr2DShape {
+  int lanes_x = 1;             // lanes along x (a power of two; 256 / lanes_x along y)
+  int cols_per_lane = 1;       // 1..4: a panel is lanes_x * cols_per_lane columns
+  uint64_t rows_per_item = 1;  // rows of the longest stretch (the rows are dealt evenly)
+  uint64_t stretches = 1, panels = 1;
+  uint64_t items = 1;          // panels * stretches, item = panel * stretches + stretch
+  uint64_t items_per_wg = 1;   // workgroup w takes items [w * items_per_wg, ...)
+  int workgroups = 1;
+  uint64_t lane_samples = 1;   // the largest per-lane sample count (32-bit in the kernel)
+};
+// How a launch over all nx columns of row_count rows is dealt out (no device needed; grid:
+// the workgroup cap, 0 = 2048). A function of (nx, row_count, grid) only. For nx * row_count
+// >= 2^20 more than half of workgroups * 256 * lane_samples are real samples. Throws, naming
+// the numbers, when no shape keeps the per-lane count below 2^32.
+Expr2DShape expr2d_shape(uint64_t nx, uint64_t row_count, int grid = 0);
+// Throws, naming the numbers, unless 1 <= nx < 2^32, 1 <= ny <= 2^40, rows [row_begin,
+// row_begin + row_count) lie in [0, ny) without wrapping and the shape exists. No device
+// needed; nothing is launched after a refusal.
+void expr2d_check(uint64_t nx, uint64_t ny, uint64_t row_begin, uint64_t row_count,
+                  int grid = 0);
+// expr2d_check, then the shape the launch of that slice uses: expr2d_shape(nx, row_count,
+// grid), which row_begin never reaches (no items and no workgroups when row_count == 0).
+// ExprIntegrator2D asks once per integrate / time call.
+Expr2DShape expr2d_plan(uint64_t nx, uint64_t ny, uint64_t row_begin, uint64_t row_count,
+                        int grid = 0);
+namespace detail {
+// expr_check with the expression itself named in the error (expr2d_source, HostExpr2D).
+void expr_check_named(const std::string& expr);
+}  // namespace detail
+
+class ExprIntegrator2D {
+ public:
+  ExprIntegrator2D(const std::string& expr, int device = 0, int grid = 0);
+  ~ExprIntegrator2D();
+  ExprIntegrator2D(const ExprIntegrator2D&) = delete;
+  ExprIntegrator2D& operator=(const ExprIntegrator2D&) = delete;
+  // S * ((hx * hy) * scale), S the sum of f(x_i, y_j) over all nx columns of rows
+  // [row_begin, row_begin + row_count); row_count == 0 gives 0.0. With a communicator of
+  // more than one rank the ranks' values are all-reduced. Synchronous.
+  double integrate(double ax, double bx, uint64_t nx, double ay, double by, uint64_t ny,
+                   Rule rule, uint64_t row_begin, uint64_t row_count, double scale = 1.0,
+                   const Comm* comm = nullptr);
+  // Device ms per integration over `iters` back-to-back ones; hooks as ExprIntegrator::time.
+  double time(double ax, double bx, uint64_t nx, double ay, double by, uint64_t ny, Rule rule,
+              uint64_t row_begin, uint64_t row_count, int iters,
+              const std::function<void()>& at_start = {},
+              const std::function<void()>& at_end = {});
+  const std::string& expression() const { return expr_; }
+
+ private:
+  void enqueue(const Expr2DShape& sh, double ax, double hx, double ay, double hy, double off,
+               uint64_t nx, uint64_t row_begin, uint64_t row_count, double scale,
+               hipStream_t s);
+  std::string expr_;
+  int device_, grid_;
+  hipModule_t module_ = nullptr;
+  hipFunction_t partials_fn_ = nullptr, finalize_fn_ = nullptr;
+  Stream stream_;
+  DeviceBuffer<double> partials_, out_;
+  PinnedBuffer<double> host_;
+  Event e0_, e1_;
+};
+
 }  // namespace miint

@@ -119,6 +119,24 @@ class HostExprSweep {
   void* fn_ = nullptr;
 };
 
+// A double integral on the host: f(x, y) over the nx x ny samples of [ax, bx] x [ay, by] from
+// the same generator and compiler path (cached per expression). Threads take balanced
+// contiguous runs of the rows, added in thread order; the value is ExprIntegrator2D's
+// (miint/expr.hpp): S * ((hx * hy) * scale) over all nx columns of rows [row_begin,
+// row_begin + row_count). The --device cpu side of the 2-D path and its CPU reference.
+class HostExpr2D {
+ public:
+  explicit HostExpr2D(const std::string& expr);
+  double integrate(double ax, double bx, uint64_t nx, double ay, double by, uint64_t ny,
+                   Rule rule, uint64_t row_begin, uint64_t row_count, HostPool& pool,
+                   double scale = 1.0) const;
+  const std::string& expression() const { return expr_; }
+
+ private:
+  std::string expr_;
+  void* fn_ = nullptr;
+};
+
 // Host collectives across processes: a TCP star through rank 0 (rank 0 listens on
 // addr:port, every other rank connects once and keeps its socket). Reductions sum in rank
 // order on rank 0, so every rank receives bitwise the same values. Every receive is bounded

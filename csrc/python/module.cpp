@@ -900,6 +900,73 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprScan::expression);
 
+  // double integrals: f(x, y) over the nx x ny samples of a rectangle
+  m.attr("EXPR2D_MAX_NX") = kExpr2DMaxNx;
+  m.attr("EXPR2D_MAX_NY") = kExpr2DMaxNy;
+  m.attr("EXPR2D_MAX_GRID") = kExpr2DMaxGrid;
+  m.def("expr2d_source", &expr2d_source, py::arg("expr"),
+        "kernel source generated for an expression over x and y");
+  m.def("expr2d_compile", [](const std::string& e) {
+          std::string code;
+          {
+            py::gil_scoped_release nogil;
+            code = expr2d_compile(e);
+          }
+          return py::bytes(code);
+        },
+        py::arg("expr"),
+        "compile a 2-D expression for gfx950 with hipRTC (no device needed); the code object");
+  py::class_<Expr2DShape>(m, "Expr2DShape", "how a 2-D launch is dealt out (expr2d_shape)")
+      .def_readonly("lanes_x", &Expr2DShape::lanes_x)
+      .def_readonly("cols_per_lane", &Expr2DShape::cols_per_lane)
+      .def_readonly("rows_per_item", &Expr2DShape::rows_per_item)
+      .def_readonly("stretches", &Expr2DShape::stretches)
+      .def_readonly("panels", &Expr2DShape::panels)
+      .def_readonly("items", &Expr2DShape::items)
+      .def_readonly("items_per_wg", &Expr2DShape::items_per_wg)
+      .def_readonly("workgroups", &Expr2DShape::workgroups)
+      .def_readonly("lane_samples", &Expr2DShape::lane_samples)
+      .def("as_tuple", [](const Expr2DShape& s) {
+        return py::make_tuple(s.lanes_x, s.cols_per_lane, s.rows_per_item, s.items,
+                              s.items_per_wg, s.workgroups);
+      }, "(lanes along x, columns per lane, rows per item, items, items per workgroup, "
+         "workgroups)");
+  m.def("expr2d_shape", &expr2d_shape, py::arg("nx"), py::arg("row_count"), py::arg("grid") = 0,
+        "launch shape of all nx columns of row_count rows: a function of these three only");
+  m.def("expr2d_check", &expr2d_check, py::arg("nx"), py::arg("ny"), py::arg("row_begin"),
+        py::arg("row_count"), py::arg("grid") = 0,
+        "raise unless the rule and the row slice are ones a 2-D launch accepts");
+  m.def("expr2d_plan", &expr2d_plan, py::arg("nx"), py::arg("ny"), py::arg("row_begin"),
+        py::arg("row_count"), py::arg("grid") = 0,
+        "expr2d_check, then the shape ExprIntegrator2D launches that slice with");
+  m.def("fma_coords", [](uint64_t first, uint64_t count, double off, double h, double a) {
+          py::array_t<double> out(static_cast<py::ssize_t>(count));
+          double* p = out.mutable_data();
+          for (uint64_t i = 0; i < count; ++i)
+            p[i] = std::fma(static_cast<double>(first + i) + off, h, a);
+          return out;
+        },
+        py::arg("first"), py::arg("count"), py::arg("off"), py::arg("h"), py::arg("a"),
+        "fma((double)i + off, h, a) for i in [first, first + count): the coordinates the "
+        "expression kernels form, rounded once");
+  py::class_<ExprIntegrator2D>(m, "ExprIntegrator2D",
+                               "f(x, y) as an expression over a rectangle (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int, int>(), py::arg("expr"), py::arg("device") = 0,
+           py::arg("grid") = 0)
+      .def("integrate", &ExprIntegrator2D::integrate, py::arg("ax"), py::arg("bx"),
+           py::arg("nx"), py::arg("ay"), py::arg("by"), py::arg("ny"), py::arg("rule"),
+           py::arg("row_begin"), py::arg("row_count"), py::arg("scale") = 1.0,
+           py::arg("comm") = nullptr, py::call_guard<py::gil_scoped_release>())
+      .def("time",
+           [](ExprIntegrator2D& e, double ax, double bx, uint64_t nx, double ay, double by,
+              uint64_t ny, Rule rule, uint64_t row_begin, uint64_t row_count, int iters) {
+             return e.time(ax, bx, nx, ay, by, ny, rule, row_begin, row_count, iters);
+           },
+           py::arg("ax"), py::arg("bx"), py::arg("nx"), py::arg("ay"), py::arg("by"),
+           py::arg("ny"), py::arg("rule"), py::arg("row_begin"), py::arg("row_count"),
+           py::arg("iters"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprIntegrator2D::expression);
+
   // ------------------------------------------------------------------ host (CPU) engine
   m.def("host_isa", &host_isa, "vector ISA the host kernels dispatch to: avx512|avx2|base");
   py::class_<HostPool>(m, "HostPool", "persistent host worker threads (0 = one per core)")
@@ -936,6 +1003,14 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("begin"), py::arg("count"), py::arg("pool"))
       .def_property_readonly("expression", &HostExprSweep::expression)
       .def_property_readonly("nparams", &HostExprSweep::nparams);
+  py::class_<HostExpr2D>(m, "HostExpr2D", "f(x, y) as an expression, on the host cores")
+      .def(py::init<const std::string&>(), py::arg("expr"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("integrate", &HostExpr2D::integrate, py::arg("ax"), py::arg("bx"), py::arg("nx"),
+           py::arg("ay"), py::arg("by"), py::arg("ny"), py::arg("rule"), py::arg("row_begin"),
+           py::arg("row_count"), py::arg("pool"), py::arg("scale") = 1.0,
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &HostExpr2D::expression);
   m.def("host_riemann_mpi_parity", &host_riemann_mpi_parity, py::arg("comm_size"), py::arg("n"),
         py::arg("range"), py::arg("pool"), py::call_guard<py::gil_scoped_release>(),
         "the reference's mpirun -np P ./riemann, bit for bit, with its P-1 workers on threads");

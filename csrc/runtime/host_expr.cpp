@@ -83,6 +83,46 @@ using namespace std;
 )";
 }
 
+using Sum2DFn = double (*)(double ax, double hx, double ay, double hy, double off,
+                           unsigned long long nx, unsigned long long j0,
+                           unsigned long long rows);
+
+// compile_host's key for f(x, y) (HostExpr2D), next to nparams < 0 (f(x)) and >= 0 (sweeps).
+constexpr int kHost2D = -2;
+
+// f(x, y) over all nx columns of rows [j0, j0 + rows): row by row, a row summed as
+// host_source sums a slice (blocks of 4096 columns, 8 accumulators, compensated block sums
+// carried across the rows).
+std::string host_source2d(const std::string& expr) {
+  return R"(#include <cmath>
+using namespace std;
+static inline double miint_f2(double x, double y) { (void)x; (void)y; return ()" + expr + R"(); }
+extern "C" double miint_host_expr2d_sum(double ax, double hx, double ay, double hy, double off,
+                                        unsigned long long nx, unsigned long long j0,
+                                        unsigned long long rows) {
+  double total = 0.0, comp = 0.0;
+  for (unsigned long long j = 0; j < rows; ++j) {
+    const double y = fma((double)(j0 + j) + off, hy, ay);
+    for (unsigned long long done = 0; done < nx;) {
+      const unsigned long long m = nx - done < 4096ull ? nx - done : 4096ull;
+      double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      const double base = (double)done + off;
+      unsigned long long k = 0;
+      for (; k + 8 <= m; k += 8)
+        for (int l = 0; l < 8; ++l) acc[l] += miint_f2(fma(base + (double)(k + l), hx, ax), y);
+      for (; k < m; ++k) acc[0] += miint_f2(fma(base + (double)k, hx, ax), y);
+      const double s = ((acc[0] + acc[4]) + (acc[2] + acc[6])) + ((acc[1] + acc[5]) + (acc[3] + acc[7]));
+      const double c = s - comp, t = total + c;
+      comp = (t - total) - c;
+      total = t;
+      done += m;
+    }
+  }
+  return total;
+}
+)";
+}
+
 std::string host_compiler() {
   if (const char* c = std::getenv("MIINT_HOST_CXX")) return c;
   struct stat st;
@@ -124,7 +164,7 @@ void check_not_profiled() {
 
 struct Compiled {
   void* handle = nullptr;
-  void* fn = nullptr;  // SumFn (nparams < 0) or SweepSumFn
+  void* fn = nullptr;  // SumFn (nparams < 0), Sum2DFn (kHost2D) or SweepSumFn
 };
 
 Compiled compile_host(const std::string& expr, int nparams = -1) {
@@ -141,7 +181,7 @@ Compiled compile_host(const std::string& expr, int nparams = -1) {
   const std::string src = dir + "/f.cpp", so = dir + "/f.so", log = dir + "/log.txt";
   {
     std::ofstream f(src);
-    f << host_source(expr, nparams);
+    f << (nparams == kHost2D ? host_source2d(expr) : host_source(expr, nparams));
   }
   check_not_profiled();
   const int rc = run_child({host_compiler(), "-std=c++17", "-O3", "-march=native", "-fPIC",
@@ -164,7 +204,9 @@ Compiled compile_host(const std::string& expr, int nparams = -1) {
   const std::string dl_err = c.handle ? "" : ::dlerror();
   cleanup();
   MIINT_CHECK(c.handle != nullptr, "host expression: dlopen: " + dl_err);
-  c.fn = ::dlsym(c.handle, nparams < 0 ? "miint_host_expr_sum" : "miint_host_expr_sweep_sum");
+  c.fn = ::dlsym(c.handle, nparams == kHost2D ? "miint_host_expr2d_sum"
+                           : nparams < 0      ? "miint_host_expr_sum"
+                                              : "miint_host_expr_sweep_sum");
   MIINT_CHECK(c.fn != nullptr, "host expression: symbol missing");
   return cache[key] = c;
 }
@@ -230,6 +272,38 @@ std::vector<double> HostExprSweep::integrate(const std::vector<double>& params, 
     out[k] = s * h;
   }
   return out;
+}
+
+HostExpr2D::HostExpr2D(const std::string& expr) : expr_(expr) {
+  detail::expr_check_named(expr);
+  fn_ = compile_host(expr, kHost2D).fn;
+}
+
+double HostExpr2D::integrate(double ax, double bx, uint64_t nx, double ay, double by,
+                             uint64_t ny, Rule rule, uint64_t row_begin, uint64_t row_count,
+                             HostPool& pool, double scale) const {
+  MIINT_CHECK(nx >= 1 && nx <= kExpr2DMaxNx,
+              "host expression 2-D: nx = " + std::to_string(nx) + " must be 1..2^32 - 1");
+  MIINT_CHECK(ny >= 1 && ny <= kExpr2DMaxNy,
+              "host expression 2-D: ny = " + std::to_string(ny) + " must be 1..2^40");
+  MIINT_CHECK(row_begin + row_count >= row_begin && row_begin + row_count <= ny,
+              "host expression 2-D: rows [" + std::to_string(row_begin) + ", " +
+                  std::to_string(row_begin) + " + " + std::to_string(row_count) +
+                  ") outside [0, " + std::to_string(ny) + ")");
+  if (row_count == 0) return 0.0;  // +0.0 whatever the signs of the steps, as the GPU gives
+  const Sum2DFn fn = reinterpret_cast<Sum2DFn>(fn_);
+  const double hx = (bx - ax) / static_cast<double>(nx);
+  const double hy = (by - ay) / static_cast<double>(ny), off = rule_offset(rule);
+  const int T = pool.threads();
+  std::vector<double> part(T, 0.0);
+  pool.run([&](int t) {
+    uint64_t tb = 0, tc = 0;
+    rank_slice(row_count, t, T, &tb, &tc);
+    if (tc) part[t] = fn(ax, hx, ay, hy, off, nx, row_begin + tb, tc);
+  });
+  double s = 0.0;
+  for (int t = 0; t < T; ++t) s += part[t];  // thread order
+  return s * ((hx * hy) * scale);
 }
 
 }  // namespace miint

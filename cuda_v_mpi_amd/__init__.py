@@ -18,7 +18,9 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     f(x, p0..p7) over K parameter rows per launch (``integrate_expr_sweep``,
     ``riemann --expr ... --params FILE``), and its running integral as a curve: F(x) at
     every sample, or every K-th one, in one call (``integrate_expr_running``,
-    ``ops.kernels.riemann_expr_scan``, ``riemann --expr ... --running``).
+    ``ops.kernels.riemann_expr_scan``, ``riemann --expr ... --running``), and double
+    integrals of f(x, y) over a rectangle (``integrate_expr2d``,
+    ``ops.kernels.riemann_expr2d``, ``riemann --expr ... --ya AY --yb BY``).
 
 Layout: models/ (integrands), ops/ (kernel entry points), parallel/ (decomposition,
 process groups), utils/ (fixtures, oracles, output formats), integrate.py (high-level API).
@@ -31,4 +33,5 @@ from ._native import native, require_gpu  # noqa: F401
 from .integrate import IntegrationResult, Integrator, integrate, integrate_expr  # noqa: F401
 from .integrate import SweepResult, integrate_expr_sweep  # noqa: F401
 from .integrate import RunningResult, integrate_expr_running  # noqa: F401
+from .integrate import integrate_expr2d  # noqa: F401
 from .models import integrands  # noqa: F401

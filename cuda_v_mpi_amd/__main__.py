@@ -191,6 +191,28 @@ def cmd_integrate(a) -> int:
 
         lo = 0.0 if a.a is None else a.a
         hi = 1.0 if a.b is None else a.b
+        if (a.ya is None) != (a.yb is None):
+            raise SystemExit("integrate: --ya and --yb go together (the y interval of a double "
+                             "integral)")
+        if a.ny is not None and a.ya is None:
+            raise SystemExit("integrate: --ny belongs to a double integral (--ya AY --yb BY)")
+        if a.ya is not None:  # f(x, y) on [a, b] x [ya, yb]: n x ny samples
+            from . import integrate_expr2d
+
+            if a.params or a.linspace:
+                raise SystemExit("integrate: a double integral takes no --params / --linspace")
+            on_host = a.backend == "host" or a.device == "cpu"
+            ny = int(a.n) if a.ny is None else int(a.ny)
+            r = integrate_expr2d(a.expr, lo, hi, a.ya, a.yb, int(a.n), ny, rule=a.rule,
+                                 backend="host" if on_host else "hip", analytic=a.analytic)
+            rec = {"expr": a.expr, "a": lo, "b": hi, "ya": a.ya, "yb": a.yb, "n": int(a.n),
+                   "ny": ny, "rule": a.rule, "value": r.value,
+                   "ms_per_integration": r.seconds_device * 1e3,
+                   "samples_per_s": r.subintervals_per_s}
+            if a.analytic is not None:
+                rec.update(analytic=a.analytic, abs_err=r.abs_err)
+            print(json.dumps(rec))
+            return 0
         if a.params or a.linspace:  # a parameter sweep: f(x, p0..p7), K rows per launch
             from . import integrate_expr_sweep
             from ._native import native
@@ -337,7 +359,11 @@ def main(argv=None) -> int:
                     "parameter rows (one per line), all rows in one launch")
     ig.add_argument("--linspace", default="", help="p0=LO:HI:COUNT, a one-parameter sweep")
     ig.add_argument("--device", default="gpu", choices=["gpu", "cpu"],
-                    help="sweeps: cpu = the host cores (as --backend host)")
+                    help="sweeps and double integrals: cpu = the host cores (as --backend host)")
+    ig.add_argument("--ya", type=float, default=None, help="with --yb: the double integral of "
+                    "--expr over x and y on [a, b] x [ya, yb], n x ny samples")
+    ig.add_argument("--yb", type=float, default=None)
+    ig.add_argument("--ny", type=float, default=None, help="samples along y (default: --n)")
     t2 = sub.add_parser("table2d")
     t2.add_argument("--grid", type=int, default=4096)
     t2.add_argument("--iters", type=int, default=100)

@@ -280,6 +280,87 @@ def integrate_expr(expr: str, a: float, b: float, n: int = 10**9, rule: str = "l
                              seconds_device=dev_s)
 
 
+def _fma_coords(first: int, count: int, off: float, h: float, a: float) -> torch.Tensor:
+    """fma(i + off, h, a) for i in [first, first + count) as an fp64 tensor: the coordinates the
+    expression kernels form, rounded once. torch has no fused multiply-add on the CPU, so the
+    native module forms them on the host (std::fma; no GPU needed)."""
+    from ._native import native
+
+    return torch.from_numpy(native().fma_coords(int(first), int(count), float(off), float(h),
+                                                float(a)))
+
+
+def _tree_sum(t: torch.Tensor, dim: int) -> torch.Tensor:
+    """Sum along `dim` in a fixed order: the upper half is added onto the lower half (the
+    middle element of an odd length waits a level) until one element is left, so a value
+    passes through ceil(log2(length)) additions. torch.sum's own order is not documented."""
+    t = t.movedim(dim, -1)
+    while t.shape[-1] > 1:
+        n = t.shape[-1]
+        half = n // 2
+        low = t[..., :half] + t[..., n - half:]
+        t = torch.cat([low, t[..., half:n - half]], dim=-1) if n % 2 else low
+    return t[..., 0]
+
+
+def integrate_expr2d(expr: str, ax: float, bx: float, ay: float, by: float, nx: int,
+                     ny: int | None = None, rule: str = "mid", backend: str = "hip",
+                     ctx: DistContext | None = None, threads: int = 0,
+                     analytic: float | None = None) -> IntegrationResult:
+    """The double integral of any f(x, y) given as one C++ expression over ``x`` and ``y`` on
+    the rectangle [ax, bx] x [ay, by]: nx x ny samples (ny defaults to nx), the same rule on
+    both axes, value = hx * hy * sum. ``backend="hip"``: the hipRTC-compiled gfx950 kernels
+    (``ops.kernels.riemann_expr2d``); ``"host"``: compiled for the host cores (HostExpr2D);
+    ``"cpu"``: the torch fp64 form (``expr_torch``'s subset of expressions) summed in row
+    chunks in a fixed order (``_tree_sum``), needs no GPU. This rank integrates its rows, rank_slice(ny, rank, world); world > 1
+    is reduced with torch.distributed."""
+    if rule not in ("left", "mid", "right"):
+        raise ValueError("rule must be left|mid|right")
+    nx = int(nx)
+    ny = nx if ny is None else int(ny)
+    if nx < 1 or ny < 1:
+        raise ValueError("integrate_expr2d needs nx >= 1 and ny >= 1")
+    ax, bx, ay, by = float(ax), float(bx), float(ay), float(by)
+    ctx = ctx or DistContext()
+    begin, count = decomposition.rank_slice(ny, ctx.rank, ctx.world)
+    t0 = time.perf_counter()
+    if backend == "hip":
+        from ._native import native
+
+        m = native()
+        value = m.ExprIntegrator2D(expr, ctx.device).integrate(
+            ax, bx, nx, ay, by, ny, getattr(m.Rule, rule), begin, count)
+    elif backend == "host":
+        from ._native import native
+
+        m = native()
+        value = m.HostExpr2D(expr).integrate(ax, bx, nx, ay, by, ny, getattr(m.Rule, rule),
+                                             begin, count, m.HostPool(threads))
+    elif backend == "cpu":
+        off = {"left": 0.0, "mid": 0.5, "right": 1.0}[rule]
+        hx, hy = (bx - ax) / nx, (by - ay) / ny
+        x = _fma_coords(0, nx, off, hx, ax)
+        # fixed order: a row's columns in a tree, a chunk's rows in a tree, chunks one by one
+        chunk = max(1, (1 << 22) // nx)      # rows per chunk: about 4 M samples at a time
+        total = 0.0
+        for r in range(begin, begin + count, chunk):
+            y = _fma_coords(r, min(chunk, begin + count - r), off, hy, ay).unsqueeze(1)
+            total += float(_tree_sum(_tree_sum(expr_torch(expr, x, y), 1), 0))
+        value = total * (hx * hy)
+    else:
+        raise ValueError("integrate_expr2d backend must be 'hip', 'host' or 'cpu'")
+    dev_s = time.perf_counter() - t0
+    if ctx.world > 1:
+        dev = "cuda" if ctx.backend == "nccl" else "cpu"
+        t = torch.tensor([value], dtype=torch.float64, device=dev)
+        ctx.all_reduce_sum(t)
+        value = float(t.item())
+    return IntegrationResult(value=value, analytic=float("nan") if analytic is None else analytic,
+                             n=nx * ny, integrand=f"expr2d:{expr}", rule=rule, dtype="fp64",
+                             gpus=ctx.world, seconds_wall=time.perf_counter() - t0,
+                             seconds_device=dev_s)
+
+
 @dataclasses.dataclass
 class SweepResult:
     values: list            # K values, one per parameter row
@@ -364,12 +445,14 @@ _TORCH_MATH = {
 }
 
 
-def expr_torch(expr: str, x: torch.Tensor) -> torch.Tensor:
+def expr_torch(expr: str, x: torch.Tensor, y: torch.Tensor | None = None) -> torch.Tensor:
     """The torch form of a run-time expression: f(x) element-wise in x's dtype, for an
     expression made of numbers, ``x``, + - * /, parentheses and the math functions torch has
     (sin, exp, pow, fabs, ...). The syntax tree is walked, nothing is ``eval``-ed; anything
     else (``?:``, comparisons, other names) raises ValueError: the cpu backend covers the
-    arithmetic subset of what the hipRTC backends compile."""
+    arithmetic subset of what the hipRTC backends compile. With ``y`` given the name ``y``
+    resolves to it and the result has the broadcast shape of x and y (f(x, y)); without it
+    ``y`` is an unknown name, as before."""
     import ast
 
     try:
@@ -388,6 +471,8 @@ def expr_torch(expr: str, x: torch.Tensor) -> torch.Tensor:
             return const(node.value)
         if isinstance(node, ast.Name) and node.id == "x":
             return x
+        if isinstance(node, ast.Name) and node.id == "y" and y is not None:
+            return y
         if isinstance(node, ast.BinOp) and type(node.op) in binops:
             return binops[type(node.op)](walk(node.left), walk(node.right))
         if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
@@ -399,6 +484,8 @@ def expr_torch(expr: str, x: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"the cpu backend does not evaluate {ast.dump(node)[:60]} "
                          f"(expression {expr!r})")
 
+    if y is not None:
+        return walk(tree) + torch.zeros_like(x + y)
     return walk(tree) + torch.zeros_like(x)  # a constant expression still has x's shape
 
 

@@ -429,6 +429,29 @@ def riemann_expr_sweep(expr: str, params, a: float, b: float, n: int, rule: str 
     return torch.as_tensor(vals, dtype=torch.float64).to(dev)
 
 
+_EXPR2D_CACHE: dict = {}
+
+
+def riemann_expr2d(expr: str, ax: float, bx: float, nx: int, ay: float, by: float, ny: int,
+                   rule: str = "left", row_begin: int = 0, rows: int | None = None,
+                   grid: int = 0) -> float:
+    """Double Riemann sum of any f(x, y) given as one C++ expression over ``x`` and ``y``
+    (``"exp(-(x*x+y*y))"``; it need not mention ``y``) on [ax, bx] x [ay, by]: nx x ny samples,
+    the same rule on both axes, compiled for gfx950 with hipRTC (csrc/runtime/expr2d.cpp) and
+    cached with its module per (expression, device, grid). The value is hx * hy * the sum over
+    all nx columns of sample rows [row_begin, row_begin + rows) (default: the rows from
+    row_begin on). ``grid``: the workgroup cap (0: 2048)."""
+    m = native()
+    dev = _device().index
+    key = (expr, dev, int(grid))
+    ei = _EXPR2D_CACHE.get(key)
+    if ei is None:
+        ei = _EXPR2D_CACHE[key] = m.ExprIntegrator2D(expr, dev, int(grid))
+    rows = ny - row_begin if rows is None else rows
+    return ei.integrate(float(ax), float(bx), int(nx), float(ay), float(by), int(ny),
+                        getattr(m.Rule, rule), int(row_begin), int(rows))
+
+
 _EXPR_SCAN_CACHE: dict = {}
 
 
