@@ -834,7 +834,9 @@ struct SinLib : Sin {
 // c_i h^i, so the b_m come out already scaled). The two samples at +-k share the even and
 // odd parts E(k^2) = b_0 + k^2 b_2 + ..., O(k^2) = b_1 + k^2 b_3 + ...: p(x_c +- k h) =
 // E +- k O, each sample its own fma and accumulation. Degree 6/7: 10 VALU per pair plus the
-// shift, ~5.9 per sample against ~10 for Horner; exact algebra, valid for any h.
+// shift, ~5.9 per sample against ~10 for Horner; exact algebra for any h at which 1 / h and
+// every c_i h^i are normal numbers (kernels.hpp poly_series_in_range: a == b and steps that
+// underflow a c_i h^i run Horner per sample instead).
 template <int NC>
 struct Poly : TileDefaults<Poly<NC>> {
   static constexpr double kScale = 1.0;

@@ -61,7 +61,8 @@ constexpr int kPolySeriesMaxCoeffs = 8;  // polynomials up to degree 7 have a se
 // With the dtype (the fp32 paths: pi4's 192-sample first-order tiles where series_ok_f32, and
 // the packed-fp32 forms of the other integrands' series tiles) and the polynomial's
 // coefficient count (Taylor-pair tiles for up
-// to kPolySeriesMaxCoeffs coefficients, exact for any h; Horner per sample otherwise).
+// to kPolySeriesMaxCoeffs coefficients, exact algebra for any h inside poly_series_in_range
+// below; Horner per sample otherwise).
 inline DivMode effective_div(DivMode d, double h, Integrand f, DType t, int ncoef = 0) {
   if (is_fp32(t)) {  // fp32: one series form per integrand (integrands_f32.hpp)
     if (d == DivMode::kIeee) return DivMode::kIeee;
@@ -127,12 +128,35 @@ inline bool pi4_series_in_range(const RiemannParams& p, DType t) {
   const double last = static_cast<double>(p.i_begin + (p.n > 0 ? p.n - 1 : 0)) + p.off;
   return std::fabs(std::fma(first, p.h, p.a)) < lim && std::fabs(std::fma(last, p.h, p.a)) < lim;
 }
+// Degenerate and tiny steps of the polynomial. The Taylor-pair tiles (integrands.hpp Poly,
+// integrands_f32.hpp PolyF32) work in steps: the host hands them cs_i = c_i h^i, they shift
+// sum cs_i u^i to u_c = x_m (1 / h) -+ 16. With h = 0 (a == b) every cs_i, i >= 1, is zero and
+// u_c infinite, so the shift's first fma is 0 * inf and every full tile is NaN where Horner
+// per sample gives p(a); a step so small that some c_i h^i is a denormal or zero loses that
+// term's low bits, or the term, where Horner per sample keeps it. So a series request keeps
+// the tiles only while h and 1 / h are finite and non-zero and every non-zero c_i has a
+// normal c_i h^i (formed as the launchers form it, in long double, rounded to double; an
+// overflow to infinity fails the test too). Otherwise the launch runs kIeee: Horner per
+// sample, which needs h for the coordinate only. NaN fails every comparison.
+inline bool poly_series_in_range(const RiemannParams& p) {
+  if (static_cast<Integrand>(p.integrand) != Integrand::kPoly) return true;
+  if (!(std::isfinite(p.h) && p.h != 0.0 && std::isfinite(1.0 / p.h))) return false;
+  long double hp = 1.0L;
+  for (int i = 0; i < p.ncoef && i < kMaxPolyCoeffs; ++i) {
+    const double cs = static_cast<double>(static_cast<long double>(p.coef[i]) * hp);
+    if (p.coef[i] != 0.0 && !std::isnormal(cs)) return false;
+    hp *= static_cast<long double>(p.h);
+  }
+  return true;
+}
 // The division a launch of `p` runs: the per-integrand choice above, and the per-sample tiles
-// for a sin / train launch with an end angle beyond kTrigSeriesMaxN quadrants or a 4/(1+x^2)
-// launch with an end coordinate beyond the series tiles' range.
+// for a sin / train launch with an end angle beyond kTrigSeriesMaxN quadrants, a 4/(1+x^2)
+// launch with an end coordinate beyond the series tiles' range or a polynomial launch whose
+// step leaves poly_series_in_range.
 inline DivMode effective_div(const RiemannParams& p, DivMode d, DType t) {
   const DivMode e = effective_div(d, p.h, static_cast<Integrand>(p.integrand), t, p.ncoef);
-  return (e != DivMode::kIeee && !(trig_series_in_range(p) && pi4_series_in_range(p, t)))
+  return (e != DivMode::kIeee &&
+          !(trig_series_in_range(p) && pi4_series_in_range(p, t) && poly_series_in_range(p)))
              ? DivMode::kIeee
              : e;
 }
