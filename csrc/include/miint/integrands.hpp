@@ -1164,7 +1164,8 @@ struct Table : TileDefaults<Table> {
   __device__ __forceinline__ double series_point(double xm, double h, int u) const {
     int lo, hi;
     ends(xm, h, lo, hi);
-    if (hi > lo + 1) return point(fma(static_cast<double>(u), h, fma(-hspan, h, xm)));
+    // every tile tile_acc sums per sample: a coarse step, and a reversed one (h < 0: hi < lo)
+    if (hi != lo && hi != lo + 1) return point(fma(static_cast<double>(u), h, fma(-hspan, h, xm)));
     double vm, D;
     Kink kn{0.0, 0.0};
     if (lo == hi) line(xm, h, lo, vm, D);

@@ -192,13 +192,16 @@ struct TableF32 : TileDefaults<TableF32> {
   __device__ __forceinline__ int segment(double t) const {
     return static_cast<int>(fmin(fmax(t, 0.0), static_cast<double>(nseg - 1)));
   }
-  // fp64 coordinate and segment, fp32 interpolation
+  // fp64 coordinate, segment and slope, fp32 interpolation. The slope is subtracted in fp64
+  // and rounded once: fl32(v1) - fl32(v0) is off by 2^-24 |v|, not 2^-24 |d|, and on the
+  // clamped end segments, where fr grows without limit, that error is multiplied by fr (two
+  // entries 87.1 and 87.100001 round to one float and the extrapolation is lost whole).
   __device__ __forceinline__ float pointf(double t) const {
     const int i = segment(t);
     const float fr = static_cast<float>(t - static_cast<double>(i));
-    const float v0 = static_cast<float>(tab[i]);
-    const float v1 = static_cast<float>(tab[i + 1]);
-    return fmaf(v1 - v0, fr, v0);
+    const double v0 = tab[i];
+    const float d = static_cast<float>(tab[i + 1] - v0);
+    return fmaf(d, fr, static_cast<float>(v0));
   }
   __device__ __forceinline__ double point(double t) const {
     return static_cast<double>(pointf(t));
