@@ -9,9 +9,13 @@
 //
 //   miint_expr_partials  2048 x 256 lanes, each a contiguous run of samples walked with an
 //                        exact fp64 index, every sample evaluated in fp64 (4 accumulators),
-//                        wave64 butterfly (__shfl_xor) + 4-wave LDS sum -> one partial per
-//                        workgroup
-//   miint_expr_finalize  one workgroup sums the partials in index order -> h * scale * sum
+//                        block reduction -> one partial per workgroup
+//   miint_expr_finalize  the closing step -> h * scale * sum
+//
+// The block reduction (wave64 butterfly over __shfl_xor, then the four waves' sums through
+// LDS) and the closing step (one workgroup sums the partials in index order, reduces and
+// scales) are the same text in every family below: the device prelude of miint/expr_rtc.hpp,
+// which also holds the compile cache, the module owner and the timing loop they share.
 //
 // Fixed grid and fixed reduction order: bitwise reproducible. Compiled programs are cached
 // per (expression, device) in the process. The expression is one C++ expression over `x`
@@ -29,6 +33,7 @@
 
 #include "miint/comm.hpp"
 #include "miint/common.hpp"
+#include "miint/expr_rtc.hpp"
 #include "miint/runtime.hpp"
 
 namespace miint {
@@ -49,7 +54,6 @@ std::string rtc_compile(const std::string& src, const std::string& expr);
 class ExprIntegrator {
  public:
   ExprIntegrator(const std::string& expr, int device, int grid = 2048);
-  ~ExprIntegrator();
   ExprIntegrator(const ExprIntegrator&) = delete;
   ExprIntegrator& operator=(const ExprIntegrator&) = delete;
   // h * scale * sum f(a + (i + off) h) over samples [begin, begin + count) of an n-sample
@@ -71,12 +75,11 @@ class ExprIntegrator {
                hipStream_t s);
   std::string expr_;
   int device_, grid_;
-  hipModule_t module_ = nullptr;
-  hipFunction_t partials_fn_ = nullptr, finalize_fn_ = nullptr;
   Stream stream_;
   DeviceBuffer<double> partials_, out_;
   PinnedBuffer<double> host_;
   Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -91,8 +94,8 @@ class ExprIntegrator {
 //                              (bx, by) walks rows by, by + gy, ...; per row it runs the
 //                              per-sample loop of miint_expr_partials over its bx share of
 //                              the samples and writes one partial per (row, bx).
-//   miint_expr_sweep_close     one workgroup per row sums the row's gx partials in index
-//                              order -> out[k] = scale * sum
+//   miint_expr_sweep_close     the closing step per row, over its gx partials
+//                              -> out[k] = scale * sum
 //
 // Rows are independent and the close is its own kernel: no workgroup waits on another, so
 // nothing depends on co-residency. gx depends on the sample count (and an explicit grid)
@@ -134,7 +137,6 @@ std::vector<double> linspace_param_rows(const std::string& spec);
 class ExprSweep {
  public:
   ExprSweep(const std::string& expr, int nparams, int device = 0, int grid = 0);
-  ~ExprSweep();
   ExprSweep(const ExprSweep&) = delete;
   ExprSweep& operator=(const ExprSweep&) = delete;
   // out[k] = h * scale * sum f(a + (i + off) h, params[k*nparams ..]) over samples
@@ -163,12 +165,11 @@ class ExprSweep {
                SweepShape shape, double scale, hipStream_t s);
   std::string expr_;
   int nparams_, device_, grid_;
-  hipModule_t module_ = nullptr;
-  hipFunction_t partials_fn_ = nullptr, close_fn_ = nullptr;
   Stream stream_;
   DeviceBuffer<double> params_, partials_, out_;
   PinnedBuffer<double> host_params_, host_out_;
   Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -234,7 +235,6 @@ struct ExprScanResult {
 class ExprScan {
  public:
   ExprScan(const std::string& expr, int device = 0);
-  ~ExprScan();
   ExprScan(const ExprScan&) = delete;
   ExprScan& operator=(const ExprScan&) = delete;
   // Writes F_i = scale * h * sum_{begin <= j <= i} f(x_j) for the selected samples of
@@ -259,14 +259,13 @@ class ExprScan {
                      hipStream_t s);
   std::string expr_;
   int device_;
-  hipModule_t module_ = nullptr;
-  hipFunction_t sums_fn_ = nullptr, prefix_fn_ = nullptr, write_fn_ = nullptr;
   Stream stream_;
   DeviceBuffer<double> local_;    // L[t]: grows on demand, kept across calls
   DeviceBuffer<double> runs_;     // A[b], then B[b]: 2 x kExprScanMaxRuns
   DeviceBuffer<double> scalars_;  // [0] T, [1] C, [2..) the ranks' gathered T
   PinnedBuffer<double> host_;           // the ranks' T (one without a communicator)
   Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -283,10 +282,9 @@ class ExprScan {
 //                          lane forms its columns' x once per item, then per row y once and
 //                          per sample f and one add (cpl accumulators); what f does with x
 //                          alone is hoisted out of the row loop by the compiler. A workgroup
-//                          takes a contiguous run of items; wave64 butterfly + 4-wave LDS sum
-//                          -> one partial per workgroup
-//   miint_expr2d_finalize  one workgroup sums the partials in index order
-//                          -> ((hx * hy) * scale) * sum
+//                          takes a contiguous run of items; block reduction -> one partial
+//                          per workgroup
+//   miint_expr2d_finalize  the closing step -> ((hx * hy) * scale) * sum
 //
 // Sample (i, j) sits at x_i = fma((double)i + off, hx, ax), y_j = fma((double)j + off, hy, ay):
 // the bits ExprIntegrator gives a coordinate. A launch covers all nx columns of rows
@@ -335,7 +333,6 @@ void expr_check_named(const std::string& expr);
 class ExprIntegrator2D {
  public:
   ExprIntegrator2D(const std::string& expr, int device = 0, int grid = 0);
-  ~ExprIntegrator2D();
   ExprIntegrator2D(const ExprIntegrator2D&) = delete;
   ExprIntegrator2D& operator=(const ExprIntegrator2D&) = delete;
   // S * ((hx * hy) * scale), S the sum of f(x_i, y_j) over all nx columns of rows
@@ -357,12 +354,11 @@ class ExprIntegrator2D {
                hipStream_t s);
   std::string expr_;
   int device_, grid_;
-  hipModule_t module_ = nullptr;
-  hipFunction_t partials_fn_ = nullptr, finalize_fn_ = nullptr;
   Stream stream_;
   DeviceBuffer<double> partials_, out_;
   PinnedBuffer<double> host_;
   Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
 }  // namespace miint

@@ -74,6 +74,20 @@ std::vector<double> param_rows(const ParamRows& obj, int nparams, uint64_t* rows
   return std::vector<double>(arr.data(), arr.data() + arr.size());
 }
 
+// A binding of a hipRTC compile (expr_compile and its kin): the GIL released, the code object
+// as bytes.
+template <class... A>
+auto compiled(std::string (*compile)(A...)) {
+  return [compile](A... a) {
+    std::string code;
+    {
+      py::gil_scoped_release nogil;
+      code = compile(a...);
+    }
+    return py::bytes(code);
+  };
+}
+
 }  // namespace
 
 static const char* scan_algo_name(ScanAlgo a) {
@@ -750,14 +764,7 @@ PYBIND11_MODULE(_miint, m) {
 
   // ------------------------------------------------------------------ runtime integrands
   m.def("expr_source", &expr_source, "kernel source generated for an expression over x");
-  m.def("expr_compile", [](const std::string& e) {
-          std::string code;
-          {
-            py::gil_scoped_release nogil;
-            code = expr_compile(e);
-          }
-          return py::bytes(code);
-        },
+  m.def("expr_compile", compiled(&expr_compile),
         "compile an expression for gfx950 with hipRTC (no device needed); the code object");
   py::class_<ExprIntegrator>(m, "ExprIntegrator",
                              "f(x) given as an expression, compiled with hipRTC for gfx950")
@@ -776,14 +783,7 @@ PYBIND11_MODULE(_miint, m) {
   // parameter sweeps: f(x, p0..p7) over K rows per launch
   m.def("expr_sweep_source", &expr_sweep_source, py::arg("expr"), py::arg("nparams"),
         "kernel source generated for an expression over x and p0..p{nparams-1}");
-  m.def("expr_sweep_compile", [](const std::string& e, int nparams) {
-          std::string code;
-          {
-            py::gil_scoped_release nogil;
-            code = expr_sweep_compile(e, nparams);
-          }
-          return py::bytes(code);
-        },
+  m.def("expr_sweep_compile", compiled(&expr_sweep_compile),
         py::arg("expr"), py::arg("nparams"),
         "compile a sweep expression for gfx950 with hipRTC (no device needed); the code object");
   m.attr("SWEEP_MAX_GRID") = kSweepMaxGrid;
@@ -847,14 +847,7 @@ PYBIND11_MODULE(_miint, m) {
   m.attr("EXPR_SCAN_MAX_TILES") = kExprScanMaxTiles;
   m.def("expr_scan_source", &expr_scan_source, py::arg("expr"),
         "source of the running-integral kernels generated for an expression over x");
-  m.def("expr_scan_compile", [](const std::string& e) {
-          std::string code;
-          {
-            py::gil_scoped_release nogil;
-            code = expr_scan_compile(e);
-          }
-          return py::bytes(code);
-        },
+  m.def("expr_scan_compile", compiled(&expr_scan_compile),
         py::arg("expr"),
         "compile the running-integral kernels for gfx950 with hipRTC (no device needed)");
   m.def("expr_scan_shape", [](uint64_t count) {
@@ -906,14 +899,7 @@ PYBIND11_MODULE(_miint, m) {
   m.attr("EXPR2D_MAX_GRID") = kExpr2DMaxGrid;
   m.def("expr2d_source", &expr2d_source, py::arg("expr"),
         "kernel source generated for an expression over x and y");
-  m.def("expr2d_compile", [](const std::string& e) {
-          std::string code;
-          {
-            py::gil_scoped_release nogil;
-            code = expr2d_compile(e);
-          }
-          return py::bytes(code);
-        },
+  m.def("expr2d_compile", compiled(&expr2d_compile),
         py::arg("expr"),
         "compile a 2-D expression for gfx950 with hipRTC (no device needed); the code object");
   py::class_<Expr2DShape>(m, "Expr2DShape", "how a 2-D launch is dealt out (expr2d_shape)")

@@ -1,8 +1,6 @@
 // Double integrals of a runtime integrand: f(x, y) over a rectangle (see miint/expr.hpp,
 // ExprIntegrator2D).
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #include "miint/expr.hpp"
 
@@ -10,6 +8,13 @@ namespace miint {
 
 namespace {
 constexpr int kExpr2DBlock = 256;
+enum { kPartials, kFinalize };  // module_'s kernels
+
+int checked_grid(int grid) {
+  MIINT_CHECK(grid >= 0 && grid <= kExpr2DMaxGrid,
+              "expression 2-D: grid must be 0 (auto) ..2048");
+  return grid;
+}
 using u128 = unsigned __int128;
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return a / b + (a % b ? 1 : 0); }
@@ -28,7 +33,7 @@ void expr_check_named(const std::string& expr) {
 
 std::string expr2d_source(const std::string& expr) {
   detail::expr_check_named(expr);
-  return R"(
+  return std::string(detail::kRtcPrelude) + R"(
 __device__ __forceinline__ double miint_f2(double x, double y) {
   (void)x; (void)y;
   return ()" + expr + R"();
@@ -101,34 +106,20 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr2d_partials(
     }
   }
   double v = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // wave64 butterfly
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  MIINT_BLOCK_SUM(v, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = MIINT_RED(red);
 }
 
-// One workgroup: thread t sums partials t, t + 256, ... in order; fixed-order tree after.
 // scale is (hx * hy) * the caller's scale, applied once.
 extern "C" __global__ __launch_bounds__(256) void miint_expr2d_finalize(
     const double* __restrict__ partials, int n, double scale, double* __restrict__ out) {
-  __shared__ double red[4];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) v += partials[i];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+  MIINT_CLOSE(partials, n, scale, out[0]);
 }
 )";
 }
 
 std::string expr2d_compile(const std::string& expr) {
-  static std::mutex mu;
-  static std::map<std::string, std::string> cache;  // expression -> code object
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(expr);
-  if (it != cache.end()) return it->second;
-  return cache[expr] = detail::rtc_compile(expr2d_source(expr), expr);
+  return detail::rtc_compile_cached(expr2d_source(expr), expr);
 }
 
 // Every (lanes along x, columns per lane, rows per lane) candidate is priced by what the
@@ -150,12 +141,10 @@ std::string expr2d_compile(const std::string& expr) {
 // it). Ties go to the first candidate in (lx, cpl, rows) order: a pure function of
 // (nx, row_count, grid).
 Expr2DShape expr2d_shape(uint64_t nx, uint64_t row_count, int grid) {
-  MIINT_CHECK(nx >= 1 && nx <= kExpr2DMaxNx,
-              "expression 2-D: nx = " + std::to_string(nx) + " must be 1..2^32 - 1");
+  detail::check_2d_nx("expression 2-D", nx);
   MIINT_CHECK(row_count >= 1 && row_count <= kExpr2DMaxNy,
               "expression 2-D: " + std::to_string(row_count) + " rows must be 1..2^40");
-  MIINT_CHECK(grid >= 0 && grid <= kExpr2DMaxGrid,
-              "expression 2-D: grid must be 0 (auto) ..2048");
+  checked_grid(grid);
   const uint64_t cap = grid > 0 ? static_cast<uint64_t>(grid) : kExpr2DMaxGrid;
   static const uint64_t kRows[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256};
   const long double total = static_cast<long double>(nx) * static_cast<long double>(row_count);
@@ -214,14 +203,7 @@ Expr2DShape expr2d_shape(uint64_t nx, uint64_t row_count, int grid) {
 
 Expr2DShape expr2d_plan(uint64_t nx, uint64_t ny, uint64_t row_begin, uint64_t row_count,
                         int grid) {
-  MIINT_CHECK(nx >= 1 && nx <= kExpr2DMaxNx,
-              "expression 2-D: nx = " + std::to_string(nx) + " must be 1..2^32 - 1");
-  MIINT_CHECK(ny >= 1 && ny <= kExpr2DMaxNy,
-              "expression 2-D: ny = " + std::to_string(ny) + " must be 1..2^40");
-  MIINT_CHECK(row_begin + row_count >= row_begin && row_begin + row_count <= ny,
-              "expression 2-D: rows [" + std::to_string(row_begin) + ", " +
-                  std::to_string(row_begin) + " + " + std::to_string(row_count) +
-                  ") outside [0, " + std::to_string(ny) + ")");
+  detail::check_2d_range("expression 2-D", nx, ny, row_begin, row_count);
   if (row_count == 0) {  // nothing to launch
     Expr2DShape none;
     none.rows_per_item = none.stretches = none.panels = none.items = none.items_per_wg = 0;
@@ -237,25 +219,14 @@ void expr2d_check(uint64_t nx, uint64_t ny, uint64_t row_begin, uint64_t row_cou
 }
 
 ExprIntegrator2D::ExprIntegrator2D(const std::string& expr, int device, int grid)
-    : expr_(expr), device_(device), grid_(grid), stream_((set_device(device), Stream())) {
-  MIINT_CHECK(grid >= 0 && grid <= kExpr2DMaxGrid,
-              "expression 2-D: grid must be 0 (auto) ..2048");
-  const std::string code = expr2d_compile(expr);
+    : expr_(expr), device_(device), grid_(checked_grid(grid)),
+      stream_((set_device(device), Stream())),
+      module_(expr2d_compile(expr), device, stream_,
+              {"miint_expr2d_partials", "miint_expr2d_finalize"}) {
   DeviceGuard g(device);
-  MIINT_HIP(hipModuleLoadData(&module_, code.data()));
-  MIINT_HIP(hipModuleGetFunction(&partials_fn_, module_, "miint_expr2d_partials"));
-  MIINT_HIP(hipModuleGetFunction(&finalize_fn_, module_, "miint_expr2d_finalize"));
   partials_ = DeviceBuffer<double>(static_cast<size_t>(kExpr2DMaxGrid));
   out_ = DeviceBuffer<double>(1);
   host_ = PinnedBuffer<double>(1);
-}
-
-ExprIntegrator2D::~ExprIntegrator2D() {
-  if (module_) {
-    (void)hipSetDevice(device_);
-    (void)hipStreamSynchronize(stream_.get());
-    (void)hipModuleUnload(module_);
-  }
 }
 
 // row_count == 0 (a rank beyond ny): no kernel, the value is 0.0. `sh` is the call's
@@ -267,21 +238,13 @@ void ExprIntegrator2D::enqueue(const Expr2DShape& sh, double ax, double hx, doub
     MIINT_HIP(hipMemsetAsync(out_.get(), 0, sizeof(double), s));
     return;
   }
-  unsigned long long nxv = nx, row0 = row_begin, rows = row_count, stretches = sh.stretches,
-                     items = sh.items, ipw = sh.items_per_wg;
-  unsigned lx_log2 = 0, cpl = static_cast<unsigned>(sh.cols_per_lane);
+  unsigned lx_log2 = 0;
   while ((1 << lx_log2) < sh.lanes_x) ++lx_log2;
-  double* parts = partials_.get();
-  void* args[] = {&ax, &hx, &ay, &hy, &off, &nxv, &row0, &rows, &lx_log2, &cpl,
-                  &stretches, &items, &ipw, &parts};
-  MIINT_HIP(hipModuleLaunchKernel(partials_fn_, sh.workgroups, 1, 1, kExpr2DBlock, 1, 1, 0, s,
-                                  args, nullptr));
-  int nb = sh.workgroups;
-  double sc = scale;
-  double* out = out_.get();
-  void* fargs[] = {&parts, &nb, &sc, &out};
-  MIINT_HIP(hipModuleLaunchKernel(finalize_fn_, 1, 1, 1, kExpr2DBlock, 1, 1, 0, s, fargs,
-                                  nullptr));
+  module_.launch(kPartials, sh.workgroups, 1, kExpr2DBlock, s, ax, hx, ay, hy, off, nx, row_begin,
+                 row_count, lx_log2, static_cast<unsigned>(sh.cols_per_lane), sh.stretches,
+                 sh.items, sh.items_per_wg, partials_.get());
+  module_.launch(kFinalize, 1, 1, kExpr2DBlock, s, partials_.get(), sh.workgroups, scale,
+                 out_.get());
 }
 
 double ExprIntegrator2D::integrate(double ax, double bx, uint64_t nx, double ay, double by,
@@ -310,16 +273,10 @@ double ExprIntegrator2D::time(double ax, double bx, uint64_t nx, double ay, doub
   const double hy = (by - ay) / static_cast<double>(ny);
   const double off = rule_offset(rule);
   hipStream_t s = stream_.get();
-  enqueue(sh, ax, hx, ay, hy, off, nx, row_begin, row_count, hx * hy, s);  // warm
-  stream_.sync();
-  if (at_start) at_start();
-  e0_.record(s);
-  for (int i = 0; i < iters; ++i)
-    enqueue(sh, ax, hx, ay, hy, off, nx, row_begin, row_count, hx * hy, s);
-  if (at_end) at_end();
-  e1_.record(s);
-  stream_.sync();
-  return Event::elapsed_ms(e0_, e1_) / iters;
+  return detail::time_enqueues(
+      stream_, e0_, e1_, iters,
+      [&] { enqueue(sh, ax, hx, ay, hy, off, nx, row_begin, row_count, hx * hy, s); }, at_start,
+      at_end);
 }
 
 }  // namespace miint

@@ -23,8 +23,6 @@
 // total = (T_0 + T_1 + ... in rank order) * (h * scale), formed on the host from the
 // gathered T (one T without a communicator).
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #include "miint/expr.hpp"
 #include "miint/trainscan.hpp"
@@ -34,11 +32,12 @@ namespace miint {
 namespace {
 constexpr int kScanBlock = 256;
 constexpr int kPrefixBlock = 1024;
+enum { kSums, kPrefix, kWrite };  // module_'s kernels
 }  // namespace
 
 std::string expr_scan_source(const std::string& expr) {
   expr_check(expr);
-  return R"(
+  return std::string(detail::kRtcPrelude) + R"(
 typedef unsigned long long u64;
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
@@ -118,12 +117,10 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr_scan_tile_sums(
       }
     }
     double acc = (a0 + a1) + (a2 + a3);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // wave64 butterfly
-    if ((threadIdx.x & 63) == 0) red[par][threadIdx.x >> 6] = acc;
-    __syncthreads();
+    MIINT_BLOCK_SUM(acc, red[par]);
     if (threadIdx.x == 0) {
       L[t] = run;
-      run += (red[par][0] + red[par][1]) + (red[par][2] + red[par][3]);
+      run += MIINT_RED(red[par]);
     }
   }
   if (threadIdx.x == 0) A[blockIdx.x] = run;
@@ -264,12 +261,7 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr_scan_write(
 }
 
 std::string expr_scan_compile(const std::string& expr) {
-  static std::mutex mu;
-  static std::map<std::string, std::string> cache;  // expression -> code object
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(expr);
-  if (it != cache.end()) return it->second;
-  return cache[expr] = detail::rtc_compile(expr_scan_source(expr), expr);
+  return detail::rtc_compile_cached(expr_scan_source(expr), expr);
 }
 
 uint64_t expr_scan_outputs(uint64_t begin, uint64_t count, uint64_t every) {
@@ -299,7 +291,7 @@ void expr_scan_check(uint64_t n, uint64_t begin, uint64_t count, uint64_t every,
   const std::string slice = "samples [" + std::to_string(begin) + ", " + std::to_string(begin) +
                             " + " + std::to_string(count) + ")";
   MIINT_CHECK(begin + count >= begin, "expression scan: " + slice + " wrap around 2^64");
-  MIINT_CHECK(n >= 1 && begin + count <= n,
+  MIINT_CHECK(detail::slice_in_range(n, begin, count),
               "expression scan: " + slice + " lie outside [0, n = " + std::to_string(n) + ")");
   MIINT_CHECK(every >= 1, "expression scan: every must be >= 1 (got 0)");
   (void)expr_scan_shape(count);
@@ -311,22 +303,12 @@ void expr_scan_check(uint64_t n, uint64_t begin, uint64_t count, uint64_t every,
 }
 
 ExprScan::ExprScan(const std::string& expr, int device)
-    : expr_(expr), device_(device), stream_((set_device(device), Stream())) {
-  const std::string code = expr_scan_compile(expr);
+    : expr_(expr), device_(device), stream_((set_device(device), Stream())),
+      module_(expr_scan_compile(expr), device, stream_,
+              {"miint_expr_scan_tile_sums", "miint_expr_scan_tile_prefix",
+               "miint_expr_scan_write"}) {
   DeviceGuard g(device);
-  MIINT_HIP(hipModuleLoadData(&module_, code.data()));
-  MIINT_HIP(hipModuleGetFunction(&sums_fn_, module_, "miint_expr_scan_tile_sums"));
-  MIINT_HIP(hipModuleGetFunction(&prefix_fn_, module_, "miint_expr_scan_tile_prefix"));
-  MIINT_HIP(hipModuleGetFunction(&write_fn_, module_, "miint_expr_scan_write"));
   runs_ = DeviceBuffer<double>(2 * kExprScanMaxRuns);  // A, then B
-}
-
-ExprScan::~ExprScan() {
-  if (module_) {
-    (void)hipSetDevice(device_);
-    (void)hipStreamSynchronize(stream_.get());
-    (void)hipModuleUnload(module_);
-  }
 }
 
 // L grows to the largest slice seen; the scalars to the largest world. Called with the
@@ -348,16 +330,12 @@ void ExprScan::enqueue_local(double a, double h, double off, uint64_t begin, uin
     return;
   }
   const ScanShape shape = expr_scan_shape(count);
-  unsigned long long i0 = begin, n = count;
-  unsigned tiles = static_cast<unsigned>(shape.tiles), R = static_cast<unsigned>(shape.run);
-  unsigned runs = static_cast<unsigned>(shape.runs);
-  double* L = local_.get();
+  const unsigned tiles = static_cast<unsigned>(shape.tiles), R = static_cast<unsigned>(shape.run);
+  const unsigned runs = static_cast<unsigned>(shape.runs);
   double* A = runs_.get();
   double* B = A + kExprScanMaxRuns;
-  void* sargs[] = {&a, &h, &off, &i0, &n, &tiles, &R, &L, &A};
-  MIINT_HIP(hipModuleLaunchKernel(sums_fn_, runs, 1, 1, kScanBlock, 1, 1, 0, s, sargs, nullptr));
-  void* pargs[] = {&A, &runs, &B, &T};
-  MIINT_HIP(hipModuleLaunchKernel(prefix_fn_, 1, 1, 1, kPrefixBlock, 1, 1, 0, s, pargs, nullptr));
+  module_.launch(kSums, runs, 1, kScanBlock, s, a, h, off, begin, count, tiles, R, local_.get(), A);
+  module_.launch(kPrefix, 1, 1, kPrefixBlock, s, A, runs, B, T);
 }
 
 // K4: the workgroups stride over the tiles, or over the outputs once a tile holds at most
@@ -368,15 +346,12 @@ void ExprScan::enqueue_write(double a, double h, double off, uint64_t begin, uin
   const uint64_t outputs = expr_scan_outputs(begin, count, every);
   if (outputs == 0) return;
   const ScanShape shape = expr_scan_shape(count);
-  unsigned long long i0 = begin, n = count, ev = every;
-  unsigned long long items = every >= EXPR_SCAN_TILE ? outputs : shape.tiles;  // <= tiles
+  const uint64_t items = every >= EXPR_SCAN_TILE ? outputs : shape.tiles;  // <= tiles
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(items, kExprScanMaxRuns));
-  unsigned R = static_cast<unsigned>(shape.run);
-  int vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0;
-  const double* L = local_.get();
-  const double* B = runs_.get() + kExprScanMaxRuns;
-  void* args[] = {&a, &h, &off, &i0, &n, &ev, &items, &R, &vec, &L, &B, &carry, &hs, &out};
-  MIINT_HIP(hipModuleLaunchKernel(write_fn_, grid, 1, 1, kScanBlock, 1, 1, 0, s, args, nullptr));
+  const int vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0;
+  module_.launch(kWrite, grid, 1, kScanBlock, s, a, h, off, begin, count, every, items,
+                 static_cast<unsigned>(shape.run), vec, local_.get(),
+                 runs_.get() + kExprScanMaxRuns, carry, hs, out);
 }
 
 ExprScanResult ExprScan::run(double a, double b, uint64_t n, Rule rule, uint64_t begin,
@@ -426,17 +401,10 @@ double ExprScan::time(double a, double b, uint64_t n, Rule rule, uint64_t begin,
   const double h = (b - a) / static_cast<double>(n);
   const double off = rule_offset(rule);
   hipStream_t s = stream_.get();
-  auto once = [&] {
+  return detail::time_enqueues(stream_, e0_, e1_, iters, [&] {
     enqueue_local(a, h, off, begin, count, s);
     enqueue_write(a, h, off, begin, count, every, nullptr, h, out_device, s);
-  };
-  once();  // warm
-  stream_.sync();
-  e0_.record(s);
-  for (int i = 0; i < iters; ++i) once();
-  e1_.record(s);
-  stream_.sync();
-  return Event::elapsed_ms(e0_, e1_) / iters;
+  });
 }
 
 }  // namespace miint

@@ -3,8 +3,6 @@
 #include <algorithm>
 #include <cmath>
 #include <fstream>
-#include <map>
-#include <mutex>
 #include <sstream>
 
 #include "miint/expr.hpp"
@@ -13,16 +11,22 @@ namespace miint {
 
 namespace {
 constexpr int kSweepBlock = 256;
+enum { kPartials, kClose };  // module_'s kernels
 
-void check_nparams(int nparams) {
+int checked_nparams(int nparams) {
   MIINT_CHECK(nparams >= 0 && nparams <= kSweepMaxParams,
               "expression sweep: nparams must be 0.." + std::to_string(kSweepMaxParams));
+  return nparams;
+}
+int checked_grid(int grid) {
+  MIINT_CHECK(grid >= 0 && grid <= kSweepMaxGrid, "expression sweep: grid must be 0 (auto) ..2048");
+  return grid;
 }
 }  // namespace
 
 std::string expr_sweep_source(const std::string& expr, int nparams) {
   expr_check(expr);
-  check_nparams(nparams);
+  checked_nparams(nparams);
   std::string sig, load, args;  // ", double p0, ..." / "const double p0 = pr[0]; ..." / ", p0, ..."
   for (int j = 0; j < nparams; ++j) {
     const std::string p = "p" + std::to_string(j);
@@ -30,16 +34,15 @@ std::string expr_sweep_source(const std::string& expr, int nparams) {
     load += "    const double " + p + " = pr[" + std::to_string(j) + "];\n";
     args += ", " + p;
   }
-  auto f = [&](const std::string& x) { return "miint_fp(fma(" + x + ", h, av)" + args + ")"; };
-  return R"(
+  return std::string(detail::kRtcPrelude) + R"(
 __device__ __forceinline__ double miint_fp(double x)" + sig + R"() { return ()" + expr + R"(); }
+#define MIINT_AT(idx) miint_fp(fma(idx, h, av))" + args + R"()
 
 // K parameter rows in one launch. gridDim.x sample slices x gridDim.y row lanes: workgroup
 // (bx, by) walks rows k0 + by, k0 + by + gridDim.y, ... below k0 + kc. A row's parameters are
 // workgroup-uniform reads of params[k * nparams + j] (never written here). Per row the
-// per-sample loop is miint_expr_partials's: lane g owns a contiguous balanced run of the
-// slice, walked with an exact fp64 index (fma(idx, h, a) per sample), four independent
-// accumulators, wave64 butterfly, four waves through LDS. One partial per (row, bx) at
+// per-sample loop is miint_expr_partials's: the lane's share (miint_lane_share) through
+// MIINT_SAMPLE_SUM, then the block sum. One partial per (row, bx) at
 // partials[(k - k0) * gridDim.x + bx]. The per-lane count is 32-bit: the host refuses a
 // shape whose lanes would take 2^32 samples or more (expr_sweep_shape). No workgroup waits
 // on another: rows are independent and the close is a kernel of its own.
@@ -48,11 +51,8 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr_sweep_partials(
     const double* __restrict__ params, int nparams, unsigned k0, unsigned kc,
     double* __restrict__ partials) {
   __shared__ double red[2][4];  // alternating per row: one barrier per row is enough
-  const unsigned long long lanes = (unsigned long long)gridDim.x * 256ull;
-  const unsigned long long g = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  const unsigned long long q = n / lanes, r = n % lanes;
-  const unsigned long long start = g * q + (g < r ? g : r);
-  const unsigned cnt = (unsigned)(q + (g < r ? 1ull : 0ull));
+  unsigned long long start;
+  const unsigned cnt = miint_lane_share(n, &start);
   const double idx0 = (double)(i0 + start) + off;
   // a in a vector register for the whole kernel: an fma takes one scalar operand (h), and
   // inside the row loop the compiler otherwise copies a from its scalar register in every
@@ -64,62 +64,32 @@ extern "C" __global__ __launch_bounds__(256) void miint_expr_sweep_partials(
   for (unsigned k = k0 + blockIdx.y; k < k0 + kc; k += gridDim.y, par ^= 1u) {
     const double* __restrict__ pr = params + (unsigned long long)k * (unsigned)nparams;
     (void)pr;
-)" + load + R"(    double idx = idx0;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    unsigned c = 0;
-    for (; c + 4 <= cnt; c += 4) {
-      a0 += )" + f("idx") + R"(;
-      a1 += )" + f("idx + 1.0") + R"(;
-      a2 += )" + f("idx + 2.0") + R"(;
-      a3 += )" + f("idx + 3.0") + R"(;
-      idx += 4.0;
-    }
-    for (; c < cnt; ++c) {
-      a0 += )" + f("idx") + R"(;
-      idx += 1.0;
-    }
-    double acc = (a0 + a1) + (a2 + a3);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // wave64 butterfly
-    if ((threadIdx.x & 63) == 0) red[par][threadIdx.x >> 6] = acc;
-    __syncthreads();
+)" + load + R"(    MIINT_SAMPLE_SUM(acc, idx0, cnt, MIINT_AT);
+    MIINT_BLOCK_SUM(acc, red[par]);
     if (threadIdx.x == 0)
-      partials[(unsigned long long)(k - k0) * gridDim.x + blockIdx.x] =
-          (red[par][0] + red[par][1]) + (red[par][2] + red[par][3]);
+      partials[(unsigned long long)(k - k0) * gridDim.x + blockIdx.x] = MIINT_RED(red[par]);
   }
 }
 
-// One workgroup per row of the chunk: thread t sums the row's partials t, t + 256, ... in
-// order; fixed-order tree after. out[k] = scale * sum.
+// One workgroup per row of the chunk closes the row's gx partials: out[k] = scale * sum.
 extern "C" __global__ __launch_bounds__(256) void miint_expr_sweep_close(
     const double* __restrict__ partials, int gx, unsigned kc, double scale,
     double* __restrict__ out) {
-  __shared__ double red[4];
   const unsigned k = blockIdx.x;
   if (k >= kc) return;
   const double* row = partials + (unsigned long long)k * (unsigned)gx;
-  double v = 0.0;
-  for (int i = threadIdx.x; i < gx; i += 256) v += row[i];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) out[k] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+  MIINT_CLOSE(row, gx, scale, out[k]);
 }
 )";
 }
 
 std::string expr_sweep_compile(const std::string& expr, int nparams) {
-  static std::mutex mu;
-  static std::map<std::pair<std::string, int>, std::string> cache;  // -> code object
-  std::lock_guard<std::mutex> lk(mu);
-  const auto key = std::make_pair(expr, nparams);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  return cache[key] = detail::rtc_compile(expr_sweep_source(expr, nparams), expr);
+  return detail::rtc_compile_cached(expr_sweep_source(expr, nparams), expr);
 }
 
 SweepShape expr_sweep_shape(uint64_t n_local, uint64_t rows, int grid) {
   MIINT_CHECK(rows >= 1 && rows <= kSweepMaxRows, "expression sweep: rows must be 1..2^20");
-  MIINT_CHECK(grid >= 0 && grid <= kSweepMaxGrid, "expression sweep: grid must be 0 (auto) ..2048");
+  checked_grid(grid);
   SweepShape s;
   if (grid > 0) {
     s.gx = grid;
@@ -130,11 +100,8 @@ SweepShape expr_sweep_shape(uint64_t n_local, uint64_t rows, int grid) {
   }
   s.gy = static_cast<int>(
       std::min<uint64_t>(std::max<uint64_t>(kSweepMaxGrid / s.gx, 1), rows));
-  const uint64_t lanes = static_cast<uint64_t>(s.gx) * kSweepBlock;
-  MIINT_CHECK(n_local / lanes + 1 < (1ull << 32),
-              "expression sweep: " + std::to_string(n_local) + " samples over " +
-                  std::to_string(lanes) + " lanes pass the 32-bit per-lane count; use a "
-                  "larger grid or slice the samples");
+  detail::check_lane_count("expression sweep", n_local,
+                           static_cast<uint64_t>(s.gx) * kSweepBlock);
   return s;
 }
 
@@ -199,24 +166,10 @@ std::vector<double> linspace_param_rows(const std::string& spec) {
 }
 
 ExprSweep::ExprSweep(const std::string& expr, int nparams, int device, int grid)
-    : expr_(expr), nparams_(nparams), device_(device), grid_(grid),
-      stream_((set_device(device), Stream())) {
-  check_nparams(nparams);
-  MIINT_CHECK(grid >= 0 && grid <= kSweepMaxGrid, "expression sweep: grid must be 0 (auto) ..2048");
-  const std::string code = expr_sweep_compile(expr, nparams);
-  DeviceGuard g(device);
-  MIINT_HIP(hipModuleLoadData(&module_, code.data()));
-  MIINT_HIP(hipModuleGetFunction(&partials_fn_, module_, "miint_expr_sweep_partials"));
-  MIINT_HIP(hipModuleGetFunction(&close_fn_, module_, "miint_expr_sweep_close"));
-}
-
-ExprSweep::~ExprSweep() {
-  if (module_) {
-    (void)hipSetDevice(device_);
-    (void)hipStreamSynchronize(stream_.get());
-    (void)hipModuleUnload(module_);
-  }
-}
+    : expr_(expr), nparams_(checked_nparams(nparams)), device_(device), grid_(checked_grid(grid)),
+      stream_((set_device(device), Stream())),
+      module_(expr_sweep_compile(expr, nparams), device, stream_,
+              {"miint_expr_sweep_partials", "miint_expr_sweep_close"}) {}
 
 void ExprSweep::check(const std::vector<double>& params, uint64_t rows, uint64_t n,
                       uint64_t begin, uint64_t count) const {
@@ -225,8 +178,7 @@ void ExprSweep::check(const std::vector<double>& params, uint64_t rows, uint64_t
               "expression sweep: " + std::to_string(params.size()) + " parameter values for " +
                   std::to_string(rows) + " rows of " + std::to_string(nparams_));
   for (double p : params) MIINT_CHECK(std::isfinite(p), "expression sweep: non-finite parameter");
-  MIINT_CHECK(n >= 1 && begin + count <= n && begin + count >= begin,
-              "expression sweep slice outside [0, n)");
+  detail::check_slice("expression sweep", n, begin, count);
 }
 
 // Buffers grow to the largest sweep seen (at least one element each); then the rows go to
@@ -252,23 +204,16 @@ void ExprSweep::upload(const std::vector<double>& params, uint64_t rows, int gx,
 
 void ExprSweep::enqueue(double a, double h, double off, uint64_t begin, uint64_t count,
                         uint64_t rows, SweepShape shape, double scale, hipStream_t s) {
-  unsigned long long i0 = begin, n = count;
-  const double* params = params_.get();
-  double* parts = partials_.get();
-  int np = nparams_, gx = shape.gx;
-  double sc = scale;
+  const int gx = shape.gx;
   const uint64_t chunk = std::min<uint64_t>(rows, std::max<uint64_t>(kSweepMaxPartials / gx, 1));
   for (uint64_t r0 = 0; r0 < rows; r0 += chunk) {
-    unsigned k0 = static_cast<unsigned>(r0);
-    unsigned kc = static_cast<unsigned>(std::min<uint64_t>(chunk, rows - r0));
+    const unsigned k0 = static_cast<unsigned>(r0);
+    const unsigned kc = static_cast<unsigned>(std::min<uint64_t>(chunk, rows - r0));
     const unsigned gy = std::min<unsigned>(static_cast<unsigned>(shape.gy), kc);
-    void* args[] = {&a, &h, &off, &i0, &n, &params, &np, &k0, &kc, &parts};
-    MIINT_HIP(hipModuleLaunchKernel(partials_fn_, gx, gy, 1, kSweepBlock, 1, 1, 0, s, args,
-                                    nullptr));
-    double* out = out_.get() + r0;
-    void* cargs[] = {&parts, &gx, &kc, &sc, &out};
-    MIINT_HIP(hipModuleLaunchKernel(close_fn_, kc, 1, 1, kSweepBlock, 1, 1, 0, s, cargs,
-                                    nullptr));
+    module_.launch(kPartials, gx, gy, kSweepBlock, s, a, h, off, begin, count, params_.get(),
+                   nparams_, k0, kc, partials_.get());
+    module_.launch(kClose, kc, 1, kSweepBlock, s, partials_.get(), gx, kc, scale,
+                   out_.get() + r0);
   }
 }
 
@@ -302,16 +247,10 @@ double ExprSweep::time(const std::vector<double>& params, uint64_t rows, double 
   const double h = (b - a) / static_cast<double>(n);
   hipStream_t s = stream_.get();
   upload(params, rows, shape.gx, s);
-  enqueue(a, h, rule_offset(rule), begin, count, rows, shape, h, s);  // warm
-  stream_.sync();
-  if (at_start) at_start();
-  e0_.record(s);
-  for (int i = 0; i < iters; ++i)
-    enqueue(a, h, rule_offset(rule), begin, count, rows, shape, h, s);
-  if (at_end) at_end();
-  e1_.record(s);
-  stream_.sync();
-  return Event::elapsed_ms(e0_, e1_) / iters;
+  return detail::time_enqueues(
+      stream_, e0_, e1_, iters,
+      [&] { enqueue(a, h, rule_offset(rule), begin, count, rows, shape, h, s); }, at_start,
+      at_end);
 }
 
 }  // namespace miint

@@ -20,6 +20,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <tuple>
 
 #include "miint/expr.hpp"
 #include "miint/host.hpp"
@@ -36,9 +37,14 @@ using SumFn = double (*)(double a, double h, double off, unsigned long long i0,
 using SweepSumFn = double (*)(double a, double h, double off, unsigned long long i0,
                               unsigned long long n, const double* p);
 
-// nparams < 0: f(x) (HostExpr). nparams >= 0: f(x, p0..p{nparams-1}) with the row's values
-// read from p (HostExprSweep); the sample loop is the same text.
-std::string host_source(const std::string& expr, int nparams = -1) {
+// What compile_host builds: f(x) (HostExpr), f(x, p0..p{nparams-1}) (HostExprSweep) or f(x, y)
+// (HostExpr2D). nparams counts for kSweep only.
+enum class HostKind { kOne, kSweep, k2D };
+
+// kOne: f(x). kSweep: f(x, p0..p{nparams-1}) with the row's values read from p; the sample
+// loop is the same text.
+std::string host_source(const std::string& expr, HostKind kind, int nparams) {
+  const bool one = kind == HostKind::kOne;
   std::string sig, load, args;
   for (int j = 0; j < nparams; ++j) {
     const std::string p = "p" + std::to_string(j);
@@ -47,12 +53,12 @@ std::string host_source(const std::string& expr, int nparams = -1) {
     args += ", " + p;
   }
   const std::string head =
-      nparams < 0
+      one
           ? "static inline double miint_f(double x) { return (" + expr + "); }\n"
           : "static inline double miint_fp(double x" + sig + ") { return (" + expr + "); }\n"
             "#define miint_f(X) miint_fp((X)" + args + ")\n";
   const std::string entry =
-      nparams < 0
+      one
           ? "extern \"C\" double miint_host_expr_sum(double a, double h, double off, "
             "unsigned long long i0,\n                                      unsigned long long n) {\n"
           : "extern \"C\" double miint_host_expr_sweep_sum(double a, double h, double off, "
@@ -86,9 +92,6 @@ using namespace std;
 using Sum2DFn = double (*)(double ax, double hx, double ay, double hy, double off,
                            unsigned long long nx, unsigned long long j0,
                            unsigned long long rows);
-
-// compile_host's key for f(x, y) (HostExpr2D), next to nparams < 0 (f(x)) and >= 0 (sweeps).
-constexpr int kHost2D = -2;
 
 // f(x, y) over all nx columns of rows [j0, j0 + rows): row by row, a row summed as
 // host_source sums a slice (blocks of 4096 columns, 8 accumulators, compensated block sums
@@ -164,14 +167,14 @@ void check_not_profiled() {
 
 struct Compiled {
   void* handle = nullptr;
-  void* fn = nullptr;  // SumFn (nparams < 0), Sum2DFn (kHost2D) or SweepSumFn
+  void* fn = nullptr;  // SumFn (kOne), SweepSumFn (kSweep) or Sum2DFn (k2D)
 };
 
-Compiled compile_host(const std::string& expr, int nparams = -1) {
+Compiled compile_host(const std::string& expr, HostKind kind, int nparams = 0) {
   static std::mutex mu;
-  static std::map<std::pair<std::string, int>, Compiled> cache;
+  static std::map<std::tuple<HostKind, std::string, int>, Compiled> cache;
   std::lock_guard<std::mutex> lk(mu);
-  const auto key = std::make_pair(expr, nparams);
+  const auto key = std::make_tuple(kind, expr, nparams);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   expr_check(expr);
@@ -181,7 +184,7 @@ Compiled compile_host(const std::string& expr, int nparams = -1) {
   const std::string src = dir + "/f.cpp", so = dir + "/f.so", log = dir + "/log.txt";
   {
     std::ofstream f(src);
-    f << (nparams == kHost2D ? host_source2d(expr) : host_source(expr, nparams));
+    f << (kind == HostKind::k2D ? host_source2d(expr) : host_source(expr, kind, nparams));
   }
   check_not_profiled();
   const int rc = run_child({host_compiler(), "-std=c++17", "-O3", "-march=native", "-fPIC",
@@ -204,21 +207,22 @@ Compiled compile_host(const std::string& expr, int nparams = -1) {
   const std::string dl_err = c.handle ? "" : ::dlerror();
   cleanup();
   MIINT_CHECK(c.handle != nullptr, "host expression: dlopen: " + dl_err);
-  c.fn = ::dlsym(c.handle, nparams == kHost2D ? "miint_host_expr2d_sum"
-                           : nparams < 0      ? "miint_host_expr_sum"
-                                              : "miint_host_expr_sweep_sum");
+  c.fn = ::dlsym(c.handle, kind == HostKind::k2D    ? "miint_host_expr2d_sum"
+                           : kind == HostKind::kOne ? "miint_host_expr_sum"
+                                                    : "miint_host_expr_sweep_sum");
   MIINT_CHECK(c.fn != nullptr, "host expression: symbol missing");
   return cache[key] = c;
 }
 
 }  // namespace
 
-HostExpr::HostExpr(const std::string& expr) : expr_(expr) { fn_ = compile_host(expr).fn; }
+HostExpr::HostExpr(const std::string& expr) : expr_(expr) {
+  fn_ = compile_host(expr, HostKind::kOne).fn;
+}
 
 double HostExpr::integrate(double a, double b, uint64_t n, Rule rule, uint64_t begin,
                            uint64_t count, HostPool& pool) const {
-  MIINT_CHECK(n >= 1 && begin + count <= n && begin + count >= begin,
-              "host expression slice outside [0, n)");
+  detail::check_slice("host expression", n, begin, count);
   const SumFn fn = reinterpret_cast<SumFn>(fn_);
   const double h = (b - a) / static_cast<double>(n), off = rule_offset(rule);
   const int T = pool.threads();
@@ -237,7 +241,7 @@ HostExprSweep::HostExprSweep(const std::string& expr, int nparams)
     : expr_(expr), nparams_(nparams) {
   MIINT_CHECK(nparams >= 0 && nparams <= kSweepMaxParams,
               "host expression sweep: nparams must be 0..8");
-  fn_ = compile_host(expr, nparams).fn;
+  fn_ = compile_host(expr, HostKind::kSweep, nparams).fn;
 }
 
 std::vector<double> HostExprSweep::integrate(const std::vector<double>& params, uint64_t rows,
@@ -251,8 +255,7 @@ std::vector<double> HostExprSweep::integrate(const std::vector<double>& params, 
                   std::to_string(nparams_));
   for (double p : params)
     MIINT_CHECK(std::isfinite(p), "host expression sweep: non-finite parameter");
-  MIINT_CHECK(n >= 1 && begin + count <= n && begin + count >= begin,
-              "host expression sweep slice outside [0, n)");
+  detail::check_slice("host expression sweep", n, begin, count);
   const SweepSumFn fn = reinterpret_cast<SweepSumFn>(fn_);
   const double h = (b - a) / static_cast<double>(n), off = rule_offset(rule);
   const int T = pool.threads();
@@ -276,20 +279,13 @@ std::vector<double> HostExprSweep::integrate(const std::vector<double>& params, 
 
 HostExpr2D::HostExpr2D(const std::string& expr) : expr_(expr) {
   detail::expr_check_named(expr);
-  fn_ = compile_host(expr, kHost2D).fn;
+  fn_ = compile_host(expr, HostKind::k2D).fn;
 }
 
 double HostExpr2D::integrate(double ax, double bx, uint64_t nx, double ay, double by,
                              uint64_t ny, Rule rule, uint64_t row_begin, uint64_t row_count,
                              HostPool& pool, double scale) const {
-  MIINT_CHECK(nx >= 1 && nx <= kExpr2DMaxNx,
-              "host expression 2-D: nx = " + std::to_string(nx) + " must be 1..2^32 - 1");
-  MIINT_CHECK(ny >= 1 && ny <= kExpr2DMaxNy,
-              "host expression 2-D: ny = " + std::to_string(ny) + " must be 1..2^40");
-  MIINT_CHECK(row_begin + row_count >= row_begin && row_begin + row_count <= ny,
-              "host expression 2-D: rows [" + std::to_string(row_begin) + ", " +
-                  std::to_string(row_begin) + " + " + std::to_string(row_count) +
-                  ") outside [0, " + std::to_string(ny) + ")");
+  detail::check_2d_range("host expression 2-D", nx, ny, row_begin, row_count);
   if (row_count == 0) return 0.0;  // +0.0 whatever the signs of the steps, as the GPU gives
   const Sum2DFn fn = reinterpret_cast<Sum2DFn>(fn_);
   const double hx = (bx - ax) / static_cast<double>(nx);

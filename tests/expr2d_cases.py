@@ -20,7 +20,8 @@ from cuda_v_mpi_amd.parallel.decomposition import rank_slice
 from cuda_v_mpi_amd.utils import exact_riemann2d as x2
 from cuda_v_mpi_amd.utils.exact_riemann2d import Axis
 
-from expr_exact_cases import LOOPBACK_WORLDS, OFF2, RULES, WORLD, a_num_R, a_num_of, bits  # noqa: F401
+from expr_exact_cases import (LOOPBACK_WORLDS, OFF2, RULES, WORLD, a_num_R,  # noqa: F401
+                              a_num_of, bits, check_module_lifetime)
 
 BLOCK = 256                    # threads of a workgroup of the 2-D kernels
 GRIDS = (1, 3, 0)              # workgroup caps: one, three, 0 = the auto shape (2048)

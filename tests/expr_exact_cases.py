@@ -12,6 +12,7 @@ forms from them can round, so every value must have the bits of the integer sum.
 from __future__ import annotations
 
 import functools
+import gc
 from typing import NamedTuple
 
 import numpy as np
@@ -251,3 +252,16 @@ BUDGETS = {"cubic": 46.6, "quadratic": 47.9, "full-lanes": 45.8, "horner8": 44.9
 
 def bits(v) -> list:
     return np.asarray(v, dtype=np.float64).reshape(-1).view(np.uint64).tolist()
+
+
+def check_module_lifetime(make, check) -> None:
+    """The lifetime of a family's loaded module: objects A and B for one expression (B's
+    compile is a cache hit) each own their module, so B still runs after A is destroyed, and
+    a fresh C after that. make() builds an object, check(obj, what) asserts one exact launch."""
+    a, b = make(), make()
+    check(a, "A")
+    check(b, "B")
+    del a
+    gc.collect()
+    check(b, "B after A is gone")
+    check(make(), "C")

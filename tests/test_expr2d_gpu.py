@@ -288,6 +288,14 @@ def test_refusals_raise_before_any_launch(native, cuda, integrator):
     assert ei.time(*args, mid, 0, c.ay.n, 2) > 0
 
 
+def test_objects_own_their_loaded_module(native, cuda):
+    """The smallest case at grid 3: A and B for one expression, A destroyed, a fresh C."""
+    c = min(c2.SMALL_CASES, key=lambda k: k.ax.n * k.ay.n)
+    c2.check_module_lifetime(
+        lambda: native.ExprIntegrator2D(c.expr, cuda.index, 3),
+        lambda ei, what: _same(_one(native, ei, c, "mid"), c2.value(c, "mid"), what))
+
+
 # ------------------------------------------------------------------------------ 13
 def _riemann(*args):
     exe = os.path.join(REPO, "build", "bin", "riemann")

@@ -35,6 +35,27 @@ def test_expr_compile_error_carries_the_log(native):
         native.expr_compile("1.0 / (1.0 + y)")
 
 
+def test_one_compile_cache_keeps_the_families_apart(native):
+    """One string through all four compiles: the shared cache is keyed so that a family gets
+    its own kernels and nobody else's, twice the same bytes, and nparams counts."""
+    names = {"1-D": (b"miint_expr_partials", b"miint_expr_finalize"),
+             "sweep": (b"miint_expr_sweep_partials", b"miint_expr_sweep_close"),
+             "scan": (b"miint_expr_scan_tile_sums", b"miint_expr_scan_tile_prefix",
+                      b"miint_expr_scan_write"),
+             "2-D": (b"miint_expr2d_partials", b"miint_expr2d_finalize")}
+    compile_ = {"1-D": lambda: native.expr_compile("x*x"),
+                "sweep": lambda: native.expr_sweep_compile("x*x", 0),
+                "scan": lambda: native.expr_scan_compile("x*x"),
+                "2-D": lambda: native.expr2d_compile("x*x")}
+    for family, make in compile_.items():
+        code = make()
+        for other, kernels in names.items():
+            for k in kernels:
+                assert (k in code) == (other == family), (family, k)
+        assert make() == code, family
+    assert native.expr_sweep_compile("x*x", 1) != compile_["sweep"]()
+
+
 # ------------------------------------------------------------------ host side (HostExpr)
 import json  # noqa: E402
 import math  # noqa: E402

@@ -264,3 +264,28 @@ def test_sweep_object_reuse_exact(native, cuda):
         got = es.integrate(np.asarray(all_rows[:k], dtype=np.float64), c.at.a, c.at.b, c.at.n,
                            native.Rule.mid, 0, c.at.n)
         _same(got, want[:k], f"reuse {k} rows")
+
+
+# ------------------------------------------------------------------------------ lifetime
+@pytest.mark.parametrize("family", ["integrator", "sweep"])
+def test_objects_own_their_loaded_module(native, cuda, family):
+    """The cubic's 2085 samples, and three rows of its sweep, at grid 3."""
+    c, at = ec.CUBIC, ec.CUBIC.at
+    if family == "integrator":
+        def make():
+            return native.ExprIntegrator(c.expr, cuda.index, 3)
+
+        def check(ei, what):
+            want = ec.poly_value(c.coef, at, "mid", 0, at.n)
+            assert _one(native, ei, c, "mid", 0, at.n) == want, what
+    else:
+        rows = ec.CUBIC_ROWS[3:6]
+
+        def make():
+            return native.ExprSweep(ec.CUBIC_SWEEP, 4, cuda.index, 3)
+
+        def check(es, what):
+            got = es.integrate(np.asarray(rows, dtype=np.float64), at.a, at.b, at.n,
+                               native.Rule.mid, 0, at.n)
+            _same(got, ec.poly_rows_values(rows, at, "mid", 0, at.n), what)
+    ec.check_module_lifetime(make, check)

@@ -185,6 +185,17 @@ def test_object_reuse_exact(native, cuda):
         assert rec["total"] == sc.total_ref(c, "mid", sc.EDGE_BEGIN, m)
 
 
+def test_objects_own_their_loaded_module(native, cuda):
+    """8 tiles + 37 samples: A and B for one expression, A destroyed, a fresh C."""
+    c = sc.QUADRATIC
+
+    def check(es, what):
+        got, rec = _run(native, es, c.at, "mid", 0, c.at.n)
+        _expect(got, sc.running_ref(c, "mid", 0, c.at.n), what)
+        assert rec["total"] == sc.total_ref(c, "mid", 0, c.at.n), what
+    ec.check_module_lifetime(lambda: native.ExprScan(c.expr, cuda.index), check)
+
+
 # ------------------------------------------------------------------------------ 9, 10
 GAUSS = "exp(-x*x)"
 GAUSS_N = 3 * 4096 + 5          # h = 3 / 12293 is not a power of two: x rounds
