@@ -348,6 +348,7 @@ constexpr const char* kUsage =
     "                   [--block B] [--grid G] [--step-streams S] [--trig-library] [--settle N]\n"
     "                   [--no-multistep] [--slots K] [--close auto|kernel|launch] [--no-ar-host]\n"
     "                   [--work auto|static|queue] [--queue-wg-per-cu W]\n"
+    "                   [--tile auto|short|long]\n"
     "                   [--diagnose] [--slice R/W] [--timeline FILE]\n"
     "                   (--timeline: after the timed run, one batch from the timeline build of\n"
     "                   the multi-step launch, per-workgroup device-clock stamps as JSON in FILE;\n"
@@ -400,6 +401,8 @@ int main(int argc, char** argv) {
       c.close = a.str("close", c.close);
       // A-B: the batch's work dealt statically or from the queue (MIINT_MS_WORK under auto)
       c.work = a.str("work", c.work);
+      // A-B: fp64 series_exact pi4 on 384- or 1536-sample tiles (MIINT_PI4_TILE under auto)
+      c.tile = a.str("tile", c.tile);
       c.queue_wg_per_cu = static_cast<int>(a.integer("queue-wg-per-cu", 0));
       c.allreduce_to_host = !a.flag("no-ar-host");
       // --slice R/W: rank R's share of a W-GPU run's step, on this GPU

@@ -107,6 +107,12 @@ struct RiemannParams {
   // The same table rounded to fp32 by the host (the fp32 sin / train series, integrands_f32.hpp):
   // kernel arguments, so the packed constants stay in SGPR pairs instead of VGPR copies.
   float trig32[kSinTrig];
+  // Tile form of an fp64 series_exact 4/(1+x^2) launch (kernels.hpp pi4_tile_long): 0 = auto
+  // (a plan: the 1536-sample tile where the step admits it; a raw launch: the 384-sample
+  // one), 1 = short (the 384-sample tile), 2 = long (refused where the step does not admit
+  // it). Read on the host only.
+  int tile;
 };
+constexpr int kTileAuto = 0, kTileShort = 1, kTileLong = 2;
 
 }  // namespace miint

@@ -566,6 +566,240 @@ struct Pi4Wide : TileDefaults<Pi4Wide> {
 // Largest |x| for which every 1 + x^2 stays inside Pi4::recip_narrow's range.
 constexpr double kPi4NarrowMaxX = 0x1p249;
 
+// ------------------------------------------------------------------ 4/(1+x^2), fp64: the long tile
+// kSeriesExact on 1536-sample tiles of 24 sub-tiles of 64, for the steps that admit it
+// (kernels.hpp pi4_tile_long: 768 h <= 2e-6). The formulation is Pi4::tile_acc's: one
+// seed_exact per tile at its midpoint, the residuals' linear terms in closed form,
+//   sum_u e_u = U e_m + B sum_u k_u^2,   sum_u k_u^2 = (U^3 - U) / 12 = 301 989 760 (U = 1536),
+// and every sample's own residual, taken linear within its sub-tile and squared in packed fp32:
+//   e_sq(+-k) = e_c +- k A',   e_c = e_m + c0 A + (c0^2 + 341.25) B,   A' = A + 2 c0 B,
+// c0 = +-32, +-96, ..., +-736 the sub-tile's centre in steps from the midpoint, k = 1/2 ... 31 1/2
+// and 341.25 = (64^2 - 1) / 12 the mean of k^2 over a sub-tile. What is paid once per tile (seed,
+// linear sum, conversions, fold: ~30 VALU) is paid a quarter as often as on 384-sample tiles,
+// and a 64-sample sub-tile halves the centres and slopes per sample (36 v_pk_fma_f32 per 1536
+// samples against 18 per 384): 1.04 VALU per sample against 1.11.
+// A 64-sample sub-tile has 32 +-k pairs; the SGPR table holds 16 pairs as before, now
+// (k_j, k_{j+16}): v_pk_fma_f32 is VOP3P, op_sel / op_sel_hi pick one half of the scalar pair
+// for both lanes and neg_hi negates the high lane, so the one pair serves (k_j, -k_j) and
+// (k_{j+16}, -k_{j+16}) (checked bitwise on the hardware: test_pi4_long_tile_gpu.py).
+// The centre carries the mean curvature in its base, so the (c0, -c0) table alone serves:
+//   in = fma((c0, -c0), B, A),  A' = fma((c0, -c0), 2 B, A),  e_c = fma((c0, -c0), in, e_m + 341.25 B)
+// — three v_pk_fma_f32 for the two sub-tiles at +c0 (low halves) and -c0 (high halves), which
+// run one after the other; the next pair's three are issued among the first pairs of the -c0
+// sub-tile, each between a square and a residual that do not touch its registers, so no
+// packed FMA stands directly behind the packed operation it reads from. Only two centre /
+// slope register pairs are live at a time. This functor sets up no fp64 pair or centre tables.
+// Bound, with u = 2^-24 and E = 2e-6 >= |e_m| + 768 h (series_ok_long), 2 |x| s <= 1:
+//   A, B -> fp32                        u |A|, u |B|
+//   base = fl32(e_m + 341.25 B)         (the fp64 fma's rounding is 2^-29 of this one) u |base| <= u E
+//   in  = fma(c0, B, A)                 u |in|, |in| ~ |A|: with A's, times c0 <= 736: 2 u 736 h
+//                                         (the B terms: 2 * 736^2 h^2 u, < 1e-11 u)
+//   e_c = fma(c0, in, base)             u |e_c| <= u E
+//   A'  = fma(c0, 2 B, A)               u |A'| and A's u |A|, times k <= 31.5: 2 u 31.5 h
+//   e   = fma(k, A', e_c)               u |e| <= u E
+// in all |de| <= u (E + 1535 h + 2 E) <= 5 u E ~ 6.0e-13, so
+//   |d(e^2)| <= 2 |e| |de| + u e^2 <= 2.4e-18 + 2.4e-19,
+// and the omitted curvature: |k^2 - 341.25| <= 31.5^2 - 341.25 = 651, |e - e_sq| <= 651 h^2 s,
+// |e^2 - e_sq^2| <= 2 * 2e-6 * 651 * (2e-6 / 768)^2 ~ 1.8e-20: 2.7e-18 of a value of order 1 per
+// sample at the largest admitted h, under 1/40 ulp (~1e-23 at N = 1e9). The two packed fp32
+// running sums are four lanes of 384 squares of at most E^2 each: a lane's additions round at
+// most u 384 E^2 each, 4 * 384 * 384 u E^2 over 1536 samples = 384 u E^2 ~ 9.2e-17 per sample
+// at the largest admitted h (four times the short tile's 96 u E^2; 1.4e-17 at N = 1e9, where
+// E = 7.7e-7), against the 2.2e-16 of the fold's two fp64 roundings.
+struct Pi4Long : TileDefaults<Pi4Long> {
+  static constexpr double kScale = 4.0;
+  static constexpr int kKPairs = 16;              // SGPR pairs (k_j, k_{j+16})
+  static constexpr int kSub = 4 * kKPairs;        // 64 samples per sub-tile
+  static constexpr int kSubs = 24;
+  static constexpr int kTile = kSub * kSubs;      // 1536 samples per seed
+  static constexpr double kSumK2 =
+      (static_cast<double>(kTile) * kTile * kTile - kTile) / 12.0;
+  static_assert(kSumK2 == 301989760.0, "sum of squared midpoint offsets of a 1536-sample tile");
+  static constexpr double kMeanK2 = (kSub * kSub - 1) / 12.0;
+  static_assert(kMeanK2 == 341.25, "mean of k^2 over a 64-sample sub-tile");
+
+  template <DivMode M>
+  __host__ __device__ static constexpr int tile_len() {
+    static_assert(M == DivMode::kSeriesExact, "the long tile is a series_exact tile");
+    return kTile;
+  }
+  template <int U, DivMode M>
+  __device__ static constexpr double anchor() { return 0.5 * (U - 1); }
+
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  f32x2 pkf[kKPairs];     // (k_j, k_{j+16}), k_j = j + 1/2                    (SGPR)
+  f32x2 pcf[kSubs / 2];   // (c0, -c0), c0 = 32, 96, ..., 736                 (SGPR)
+
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int j = 0; j < kKPairs; ++j) {
+      const f32x2 kk = {j + 0.5f, j + kKPairs + 0.5f};
+      pkf[j] = __builtin_bit_cast(f32x2, Pi4::opaque_s(__builtin_bit_cast(double, kk)));
+    }
+#pragma unroll
+    for (int i = 0; i < kSubs / 2; ++i) {
+      const float c0 = kSub * (i + 0.5f);
+      const f32x2 cc = {c0, -c0};
+      pcf[i] = __builtin_bit_cast(f32x2, Pi4::opaque_s(__builtin_bit_cast(double, cc)));
+    }
+  }
+
+  __device__ __forceinline__ double point(double x) const { return 1.0 / fma(x, x, 1.0); }
+
+  // Pi4::seed_exact's operations (the seed's residual from the exact d_m, A from q = x_m s)
+  __device__ __forceinline__ static Pi4::Seed seed_exact(double xm, double h) {
+    const double dm = fma(xm, xm, 1.0);
+    const double s = __builtin_amdgcn_rcp(dm);
+    const double q = xm * s;
+    const double qe = fma(xm, s, -q);
+    const double em = fma(-xm, qe, fma(-xm, q, 1.0 - s));
+    return {s, em, (-2.0 * h) * q, -(h * h) * s};
+  }
+  // The tile's fp32 constants: p1 = (A, B), p2 = (e_m + 341.25 B, 2 B); the packed centre
+  // operations broadcast the half they need through op_sel.
+  struct SeedF32 {
+    f32x2 p1, p2;
+  };
+  __device__ __forceinline__ static SeedF32 seed_f32(const Pi4::Seed& sd) {
+    const float b = static_cast<float>(sd.b);
+    return {{static_cast<float>(sd.a), b}, {static_cast<float>(fma(kMeanK2, sd.b, sd.em)), b + b}};
+  }
+
+  // Slopes into AN and centres into CN of the two sub-tiles at +-c0 (C0N: the (c0, -c0) SGPR
+  // pair): CN holds `in` between the first and the third.
+#define MIINT_LC_IN(C0N, CN) \
+  "v_pk_fma_f32 %[" CN "], %[" C0N "], %[p1], %[p1] op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"
+#define MIINT_LC_A(C0N, AN) \
+  "v_pk_fma_f32 %[" AN "], %[" C0N "], %[p2], %[p1] op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"
+#define MIINT_LC_C(C0N, CN) \
+  "v_pk_fma_f32 %[" CN "], %[" C0N "], %[" CN "], %[p2] op_sel_hi:[1,1,0]\n\t"
+  // Two pairs at a time, as Pi4::subtile_squares: the residuals (+k_j, -k_j) and
+  // (+k_{j+16}, -k_{j+16}) from the two halves of one SGPR pair, then their squares into the
+  // two running sums. HALF: which half of the slope and centre pairs both lanes read.
+#define MIINT_L_LO "0"
+#define MIINT_L_HI "1"
+#define MIINT_L_PAIRS2(K, HALF)                                                            \
+  "v_pk_fma_f32 %[e0], %[" K "], %[a], %[c] op_sel:[0," HALF "," HALF "] op_sel_hi:[0," HALF \
+  "," HALF "] neg_hi:[1,0,0]\n\t"                                                          \
+  "v_pk_fma_f32 %[e1], %[" K "], %[a], %[c] op_sel:[1," HALF "," HALF "] op_sel_hi:[1," HALF \
+  "," HALF "] neg_hi:[1,0,0]\n\t"                                                          \
+  "v_pk_fma_f32 %[ta], %[e0], %[e0], %[ta]\n\t"                                            \
+  "v_pk_fma_f32 %[tb], %[e1], %[e1], %[tb]\n\t"
+#define MIINT_L_REST(HALF)                                                                   \
+  MIINT_L_PAIRS2("k4", HALF) MIINT_L_PAIRS2("k5", HALF) MIINT_L_PAIRS2("k6", HALF)           \
+  MIINT_L_PAIRS2("k7", HALF) MIINT_L_PAIRS2("k8", HALF) MIINT_L_PAIRS2("k9", HALF)           \
+  MIINT_L_PAIRS2("k10", HALF) MIINT_L_PAIRS2("k11", HALF) MIINT_L_PAIRS2("k12", HALF)        \
+  MIINT_L_PAIRS2("k13", HALF) MIINT_L_PAIRS2("k14", HALF) MIINT_L_PAIRS2("k15", HALF)
+#define MIINT_L_SUBTILE(HALF)                                                                \
+  MIINT_L_PAIRS2("k0", HALF) MIINT_L_PAIRS2("k1", HALF) MIINT_L_PAIRS2("k2", HALF)           \
+  MIINT_L_PAIRS2("k3", HALF) MIINT_L_REST(HALF)
+#define MIINT_L_SUBTILE_NEXT(HALF)                                                           \
+  MIINT_L_PAIRS2("k0", HALF) MIINT_LC_IN("c0n", "cn") MIINT_L_PAIRS2("k1", HALF)             \
+  MIINT_LC_A("c0n", "an") MIINT_L_PAIRS2("k2", HALF) MIINT_LC_C("c0n", "cn")                 \
+  MIINT_L_PAIRS2("k3", HALF) MIINT_L_REST(HALF)
+#define MIINT_L_IN                                                                            \
+  [k0] "s"(pkf[0]), [k1] "s"(pkf[1]), [k2] "s"(pkf[2]), [k3] "s"(pkf[3]), [k4] "s"(pkf[4]),   \
+  [k5] "s"(pkf[5]), [k6] "s"(pkf[6]), [k7] "s"(pkf[7]), [k8] "s"(pkf[8]), [k9] "s"(pkf[9]),   \
+  [k10] "s"(pkf[10]), [k11] "s"(pkf[11]), [k12] "s"(pkf[12]), [k13] "s"(pkf[13]),             \
+  [k14] "s"(pkf[14]), [k15] "s"(pkf[15]), [a] "v"(a), [c] "v"(c)
+  // The 64 samples of the sub-tile at -c0 (Hi) or +c0 of the pair whose slopes and centres
+  // are `a` and `c`.
+  template <bool Hi>
+  __device__ __forceinline__ void subtile_squares(f32x2& ta, f32x2& tb, f32x2 a, f32x2 c) const {
+    static_assert(kKPairs == 16, "the statement names 16 pair constants");
+    f32x2 e0, e1;
+    if constexpr (Hi) {
+      asm volatile(MIINT_L_SUBTILE(MIINT_L_HI)
+                   : [e0] "=&v"(e0), [e1] "=&v"(e1), [ta] "+v"(ta), [tb] "+v"(tb)
+                   : MIINT_L_IN);
+    } else {
+      asm volatile(MIINT_L_SUBTILE(MIINT_L_LO)
+                   : [e0] "=&v"(e0), [e1] "=&v"(e1), [ta] "+v"(ta), [tb] "+v"(tb)
+                   : MIINT_L_IN);
+    }
+  }
+  // The sub-tile at -c0, and among its first pairs the slopes `an` and centres `cn` of the
+  // next pair of sub-tiles (`c0n`: their (c0, -c0)).
+  __device__ __forceinline__ void subtile_squares_next(f32x2& ta, f32x2& tb, f32x2 a, f32x2 c,
+                                                       f32x2 c0n, const SeedF32& sf, f32x2& an,
+                                                       f32x2& cn) const {
+    f32x2 e0, e1;
+    asm volatile(MIINT_L_SUBTILE_NEXT(MIINT_L_HI)
+                 : [e0] "=&v"(e0), [e1] "=&v"(e1), [an] "=&v"(an), [cn] "=&v"(cn), [ta] "+v"(ta),
+                   [tb] "+v"(tb)
+                 : MIINT_L_IN, [c0n] "s"(c0n), [p1] "v"(sf.p1), [p2] "v"(sf.p2));
+  }
+  // Slopes and centres of the tile's first pair of sub-tiles, by the same three operations.
+  __device__ __forceinline__ static void first_centres(f32x2 c0n, const SeedF32& sf, f32x2& an,
+                                                       f32x2& cn) {
+    asm volatile(MIINT_LC_IN("c0n", "cn") MIINT_LC_A("c0n", "an") MIINT_LC_C("c0n", "cn")
+                 : [an] "=&v"(an), [cn] "=&v"(cn)
+                 : [c0n] "s"(c0n), [p1] "v"(sf.p1), [p2] "v"(sf.p2));
+  }
+#undef MIINT_LC_IN
+#undef MIINT_LC_A
+#undef MIINT_LC_C
+#undef MIINT_L_LO
+#undef MIINT_L_HI
+#undef MIINT_L_PAIRS2
+#undef MIINT_L_REST
+#undef MIINT_L_SUBTILE
+#undef MIINT_L_SUBTILE_NEXT
+#undef MIINT_L_IN
+
+  template <int U, DivMode M>
+  __device__ __forceinline__ double tile_acc(double xa, double h, double acc) const {
+    static_assert(M == DivMode::kSeriesExact && U == kTile, "1536-sample series_exact tiles");
+    const Pi4::Seed sd = seed_exact(xa, h);
+    // sum_u e_u (U e_m + B sum k^2), in fp64
+    const double lin = fma(kSumK2, sd.b, static_cast<double>(U) * sd.em);
+    const SeedF32 sf = seed_f32(sd);
+    // every sample's e^2, in packed fp32: lane 0 the +k samples', lane 1 the -k samples'
+    f32x2 ta = {0.0f, 0.0f}, tb = {0.0f, 0.0f};
+    f32x2 a[2], c[2];
+    first_centres(pcf[0], sf, a[0], c[0]);
+#pragma unroll
+    for (int i = 0; i < kSubs / 2; ++i) {
+      // the sub-tiles at -c0 and +c0 one after the other: their slopes and centres die at once
+      if (i + 1 < kSubs / 2)
+        subtile_squares_next(ta, tb, a[i & 1], c[i & 1], pcf[i + 1], sf, a[(i + 1) & 1],
+                             c[(i + 1) & 1]);
+      else
+        subtile_squares<true>(ta, tb, a[i & 1], c[i & 1]);
+      subtile_squares<false>(ta, tb, a[i & 1], c[i & 1]);
+    }
+    ta += tb;
+    const double t = lin + (static_cast<double>(ta.x) + static_cast<double>(ta.y));
+    // U samples of s (1 + e + e^2): s U + s (sum e + sum e^2)
+    return fma(sd.s, t, fma(sd.s, static_cast<double>(U), acc));
+  }
+
+  // Value of sample u of a full tile (validation kernel), the long tile's mirror of
+  // Pi4::series_exact_point: the same seed, the same fp32 centre, slope, residual and square as
+  // the tile forms them (the product widened to double); the linear term is the sample's full
+  // fp64 residual e = e_m + K A + K^2 B at its offset K = u - 767.5 from the midpoint, what
+  // the tile's closed-form sum adds up over its samples.
+  __device__ __forceinline__ double series_exact_point(double xm, double h, int u) const {
+    const Pi4::Seed sd = seed_exact(xm, h);
+    const double K = static_cast<double>(u) - 0.5 * (kTile - 1);
+    const double e = fma(K, fma(K, sd.b, sd.a), sd.em);
+    const SeedF32 sf = seed_f32(sd);
+    const int q = u / kSub, w = u % kSub;
+    const bool hi = q < kSubs / 2;  // the sub-tile at -c0 reads the high halves
+    const int i = hi ? kSubs / 2 - 1 - q : q - kSubs / 2;
+    const float c0 = kSub * (i + 0.5f);
+    const f32x2 cc = {c0, -c0};
+    const f32x2 A = {sf.p1.x, sf.p1.x}, B = {sf.p1.y, sf.p1.y};
+    const f32x2 B2 = {sf.p2.y, sf.p2.y}, base = {sf.p2.x, sf.p2.x};
+    const f32x2 cs = __builtin_elementwise_fma(cc, __builtin_elementwise_fma(cc, B, A), base);
+    const f32x2 as = __builtin_elementwise_fma(cc, B2, A);
+    const float k = static_cast<float>(w) - 0.5f * (kSub - 1);
+    const float e_sq = fmaf(k, hi ? as.y : as.x, hi ? cs.y : cs.x);
+    const float sq = e_sq * e_sq;
+    return fma(sd.s, e + static_cast<double>(sq), sd.s);
+  }
+};
+
 // ------------------------------------------------------------------ tile seed: sin and cos
 // sin and cos of a tile midpoint angle, for |n| <= kTrigSeriesMaxN = 2^31 - 2^16 quadrants
 // (|theta| <= 3.3731e9; the dispatcher sends a launch with an end angle beyond it to the

@@ -101,6 +101,14 @@ struct RiemannConfig {
   // Both give the same values bit for bit (a partial depends only on its virtual block).
   // Plans that close in the launch (close = "launch") keep the static kernel.
   std::string work = "auto";
+  // Tile form of the fp64 series_exact 4/(1+x^2) kernels (kernels.hpp pi4_tile_long):
+  //   "auto":  the 1536-sample tile where the step admits it (768 h <= 2e-6), else the
+  //            384-sample one; MIINT_PI4_TILE=short|long overrides (the A/B's other side).
+  //            (The raw launchers' own auto keeps the 384-sample tile: kernels.hpp.)
+  //   "short": the 384-sample tile, as every launch ran before the long one existed;
+  //   "long":  the 1536-sample tile; refused where the step does not admit it.
+  // Every kernel form of the plan runs the same tile (RiemannPlan::tile says which).
+  std::string tile = "auto";
   int queue_wg_per_cu = 0;  // queue: physical workgroups per CU (0: the occupancy query's)
   // Bucketed batches all-reduce their step values straight into the pinned host slots
   // (RCCL's receive buffer is the mapped host memory) instead of in place on the device
@@ -329,6 +337,9 @@ class RiemannPlan {
   // How multi-step batches deal their work (RiemannConfig::work, in effect): "queue" or
   // "static" (also for plans without multi-step batches: nothing is dealt from a queue).
   const char* work() const { return multistep() && work_queue_ ? "queue" : "static"; }
+  // The tile form the plan's kernels run (RiemannConfig::tile, in effect): "long" for the
+  // 1536-sample series_exact tile, "short" for everything else.
+  const char* tile() const { return long_tile_ ? "long" : "short"; }
   // The queue launch's physical workgroups (0 for a static plan).
   int queue_workgroups() const { return multistep() && work_queue_ ? queue_wgs_ : 0; }
   // Bucketed batches enqueued directly all-reduce into pinned host memory
@@ -369,6 +380,7 @@ class RiemannPlan {
   DeviceBuffer<double> slots_;     // grid write-once slots of the fused (ticket) kernel
   DeviceBuffer<double> ms_partials_;  // multistep: slots x grid partials
   bool multistep_ = false;
+  bool long_tile_ = false;
   bool close_launch_ = false;         // multistep batches closed in-launch
   bool capturing_ = false;            // batch_graph() is capturing (enqueue_bucket_reduce)
   bool ar_host_ok_ = true;            // check_allreduce_to_host's verdict

@@ -161,6 +161,56 @@ inline DivMode effective_div(const RiemannParams& p, DivMode d, DType t) {
              : e;
 }
 
+// The long tile of the fp64 series_exact 4/(1+x^2) launches (integrands.hpp Pi4Long): 1536
+// samples per seed, the farthest 768 steps from it, under the same cap on |e| as the 384-sample
+// tile: 768 |h| <= 2e-6 (N >= 3.84e8 on a unit interval). The per-tile work (seed, linear sum,
+// conversions, fold) is then paid a quarter as often. A function of the launch's parameters,
+// dtype and division alone, so every kernel form of a plan runs the same tile and their values
+// stay bitwise equal. A degenerate interval (a == b: h = 0) keeps the 384-sample tile: there is
+// no step to be fine, and its launches go on returning 0 from the kernels that always ran them.
+// RiemannParams::tile: kTileShort never runs it, kTileLong is refused where it is not admitted.
+// kTileAuto is resolved where the launch is planned (`auto_long`): a RiemannPlan takes the long
+// tile where it is admitted (kPi4LongTileAuto: its A/B passed the bar, profiles/r20) and hands
+// its launchers the explicit form; a raw launch (launch_riemann_* with kTileAuto) keeps the
+// 384-sample tile, the length tests/test_pi4_truth_cpu.py pins for such launches at every
+// step (test_every_case_runs_the_path_it_names: that test set this limit).
+// MIINT_PI4_TILE=short|long overrides kTileAuto in both places (the A/B's other side within
+// one build, as MIINT_MS_WORK does for the queue); `long` there still runs the short tile
+// where the step does not admit the long one.
+constexpr int kSeriesHalfSpanLong = 768;
+constexpr bool kPi4LongTileAuto = true;  // a plan's kTileAuto where both tiles are admitted
+inline bool series_ok_long(double h) {
+  const double ah = h < 0 ? -h : h;
+  return ah > 0.0 && kSeriesHalfSpanLong * ah <= 2e-6;
+}
+inline bool pi4_long_admitted(const RiemannParams& p, DType t, DivMode d) {
+  return static_cast<Integrand>(p.integrand) == Integrand::kPi4 && t == DType::kF64 &&
+         d == DivMode::kSeriesExact && series_ok_long(p.h) &&
+         effective_div(p, d, t) == DivMode::kSeriesExact;
+}
+// `env`: the value of MIINT_PI4_TILE (null or empty: unset)
+inline bool pi4_tile_long(const RiemannParams& p, DType t, DivMode d, const char* env,
+                          bool auto_long = false) {
+  MIINT_CHECK(p.tile == kTileAuto || p.tile == kTileShort || p.tile == kTileLong,
+              "tile must be auto, short or long");
+  const bool ok = pi4_long_admitted(p, t, d);
+  if (p.tile == kTileLong)
+    MIINT_CHECK(ok, "tile = long needs fp64 pi4 with div = series_exact and a step of at most "
+                    "2e-6 / 768 (N >= 3.84e8 on a unit interval); this launch's does not admit it");
+  if (p.tile != kTileAuto) return p.tile == kTileLong;
+  if (env && *env) {
+    const std::string e(env);
+    MIINT_CHECK(e == "short" || e == "long", "MIINT_PI4_TILE must be short or long (got " + e + ")");
+    return ok && e == "long";
+  }
+  return ok && auto_long;
+}
+inline int tile_form_of(const std::string& s) {
+  MIINT_CHECK(s == "auto" || s == "short" || s == "long",
+              "tile must be auto, short or long (got " + s + ")");
+  return s == "auto" ? kTileAuto : s == "short" ? kTileShort : kTileLong;
+}
+
 struct LaunchShape {
   int grid;   // workgroups
   int block;  // threads per workgroup
@@ -303,6 +353,13 @@ void set_pi4_library_division(bool on);
 // the narrow reciprocal (both end coordinates below 2^249 in fp64, 2^49 in fp32, and the
 // validation switch off), false for the library division (Pi4Wide, Pi4F32Wide; fp32acc refuses).
 bool pi4_ieee_narrow(const RiemannParams& p, DType dtype);
+// Validation: the packed-fp32 source modifiers of the long tile's pair loop. For element i,
+// with a = (ac[4i], ac[4i+1]) and c = (ac[4i+2], ac[4i+3]): out[16i + 0..7] the residual pairs
+// fma((k, -k), a.half, c.half) formed from ONE scalar pair (ka, kb) through op_sel and neg_hi,
+// out[16i + 8..15] the same from the scalar pairs (ka, -ka), (kb, -kb); order (ka, low),
+// (kb, low), (ka, high), (kb, high). The two halves must agree bit for bit.
+void launch_pk_modifier_check(const float* ac, uint64_t n, float ka, float kb, float* out,
+                              hipStream_t stream);
 // Validation switch: kIeee sin (Sin) and cos (TrainVel) by ocml per sample instead of the
 // fast per-sample path (fast_trig.hpp). Process-wide; tests only.
 void set_trig_library(bool on);
@@ -316,7 +373,8 @@ void set_lds_poison_trainscan(bool on);  // (per kernel file; set_lds_poison set
 void set_lds_poison_table(bool on);
 
 // Samples per lane tile of the kernel that launch_riemann_* would run for these arguments
-// (32; 64 or 128 on the series paths): host-side grid sizing.
+// (32; 64 up to 384 on the series paths, 1536 on the long series_exact tile): host-side grid
+// sizing, the queue's items and the multi-step rotation all read it.
 int riemann_tile_len(const RiemannParams& p, DType dtype, DivMode div);
 
 // Integrand scale factor (4 for Pi4, 1 otherwise).

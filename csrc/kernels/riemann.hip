@@ -21,6 +21,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstdlib>
 #include <string>
 
 #include "miint/common.hpp"
@@ -364,6 +365,8 @@ static_assert(2 * AngleSeries<12>::kPairs + 12 == kSinTrig, "trig table sized fo
 static_assert(Pi4::kSeriesTile / 2 == kSeriesHalfSpan &&
                   Pi4F32::kSubs * Pi4F32::kSubLen / 2 == kSeriesHalfSpanF32,
               "kSeriesHalfSpan(F32) must be half the Pi4 series tile lengths");
+static_assert(Pi4Long::kTile / 2 == kSeriesHalfSpanLong,
+              "kSeriesHalfSpanLong must be half the long Pi4 tile");
 
 // ---------------------------------------------------------------------------- functor makers
 // Each integrand gets its own kernel instantiation (own register allocation); only the
@@ -373,6 +376,14 @@ template <> struct Maker<Pi4> {
   static constexpr int kLds = 1;
   __device__ static Pi4 make(const RiemannParams&, const double*, int, double*) {
     Pi4 f;
+    f.init();
+    return f;
+  }
+};
+template <> struct Maker<Pi4Long> {
+  static constexpr int kLds = 1;
+  __device__ static Pi4Long make(const RiemannParams&, const double*, int, double*) {
+    Pi4Long f;
     f.init();
     return f;
   }
@@ -1091,7 +1102,7 @@ __global__ __launch_bounds__(kMaxBlock) kFullOccupancy void riemann_queue_timeli
 // until they are measured.
 template <DivMode M, class F>
 constexpr bool queue_pays() {
-  return M == DivMode::kSeriesExact && __is_same(F, Pi4);
+  return M == DivMode::kSeriesExact && (__is_same(F, Pi4) || __is_same(F, Pi4Long));
 }
 
 // Closes a multi-step launch: workgroup s sums step s's partials in index order (finalize
@@ -1128,6 +1139,8 @@ __global__ __launch_bounds__(B) void point_values_kernel(RiemannParams p, const 
       v = full ? f.series_point(xm, p.h, u) : f.point(x);
     } else if constexpr (M == DivMode::kSeriesExact && __is_same(F, Pi4)) {
       v = full ? f.series_exact_point(xm, p.h, u) : f.point(x);
+    } else if constexpr (__is_same(F, Pi4Long)) {
+      v = full ? f.series_exact_point(xm, p.h, u) : f.point(x);
     } else if constexpr (M == DivMode::kSeries && IsPolyF64<F>::value) {
       v = full ? f.series_point(xm, u) : f.point(x);
     } else if constexpr (M == DivMode::kSeries && __is_same(F, Table)) {
@@ -1158,6 +1171,46 @@ __global__ __launch_bounds__(B) void recip_narrow_kernel(const double* d, uint64
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * B;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * B + threadIdx.x; i < n; i += stride)
     out[i] = Pi4::recip_narrow(d[i]);
+}
+// Validation of the VOP3P modifiers the long tile's pair loop rests on (Pi4Long): for every
+// element i, a slope pair a = (ac[4i], ac[4i+1]) and a centre pair c = (ac[4i+2], ac[4i+3]),
+// the residual pairs fma((k, -k), a.half, c.half) for k = ka, kb and half = low, high
+//   out[16 i + 0..7]   from ONE scalar pair (ka, kb): op_sel / op_sel_hi pick k for both lanes,
+//                      neg_hi negates the high lane (the long tile's form);
+//   out[16 i + 8..15]  from the scalar pairs (ka, -ka) and (kb, -kb) (Pi4::subtile_squares' form).
+// Order: (ka, low), (kb, low), (ka, high), (kb, high), two lanes each.
+__global__ __launch_bounds__(B) void pk_modifier_check_kernel(const float* ac, uint64_t n,
+                                                              float ka, float kb, float* out) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2 kk = __builtin_bit_cast(
+      f32x2, Pi4::opaque_s(__builtin_bit_cast(double, f32x2{ka, kb})));
+  const f32x2 kan = __builtin_bit_cast(
+      f32x2, Pi4::opaque_s(__builtin_bit_cast(double, f32x2{ka, -ka})));
+  const f32x2 kbn = __builtin_bit_cast(
+      f32x2, Pi4::opaque_s(__builtin_bit_cast(double, f32x2{kb, -kb})));
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * B + threadIdx.x;
+  if (i >= n) return;
+  const f32x2 a = {ac[4 * i], ac[4 * i + 1]}, c = {ac[4 * i + 2], ac[4 * i + 3]};
+  f32x2 r[8];
+  asm volatile(
+      "v_pk_fma_f32 %[r0], %[kk], %[a], %[c] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_hi:[1,0,0]\n\t"
+      "v_pk_fma_f32 %[r1], %[kk], %[a], %[c] op_sel:[1,0,0] op_sel_hi:[1,0,0] neg_hi:[1,0,0]\n\t"
+      "v_pk_fma_f32 %[r2], %[kk], %[a], %[c] op_sel:[0,1,1] op_sel_hi:[0,1,1] neg_hi:[1,0,0]\n\t"
+      "v_pk_fma_f32 %[r3], %[kk], %[a], %[c] op_sel:[1,1,1] op_sel_hi:[1,1,1] neg_hi:[1,0,0]\n\t"
+      : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3])
+      : [kk] "s"(kk), [a] "v"(a), [c] "v"(c));
+  asm volatile(
+      "v_pk_fma_f32 %[r0], %[ka], %[a], %[c] op_sel_hi:[1,0,0]\n\t"
+      "v_pk_fma_f32 %[r1], %[kb], %[a], %[c] op_sel_hi:[1,0,0]\n\t"
+      "v_pk_fma_f32 %[r2], %[ka], %[a], %[c] op_sel:[0,1,1]\n\t"
+      "v_pk_fma_f32 %[r3], %[kb], %[a], %[c] op_sel:[0,1,1]\n\t"
+      : [r0] "=&v"(r[4]), [r1] "=&v"(r[5]), [r2] "=&v"(r[6]), [r3] "=&v"(r[7])
+      : [ka] "s"(kan), [kb] "s"(kbn), [a] "v"(a), [c] "v"(c));
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    out[16 * i + 2 * j] = r[j].x;
+    out[16 * i + 2 * j + 1] = r[j].y;
+  }
 }
 __global__ __launch_bounds__(B) void recip_narrow_f32_kernel(const float* d, uint64_t n,
                                                              float* out) {
@@ -1339,11 +1392,20 @@ inline bool pi4_narrow(const RiemannParams& p, double max_x = kPi4NarrowMaxX) {
          std::fabs(std::fma(last, p.h, p.a)) < max_x;
 }
 
+// The tile form of an fp64 series_exact 4/(1+x^2) launch (kernels.hpp pi4_tile_long; `m` is
+// the division in effect): the same answer for every kernel form of a launch.
+inline bool pi4_long(const RiemannParams& p, DType dtype, DivMode m) {
+  return pi4_tile_long(p, dtype, m, std::getenv("MIINT_PI4_TILE"));
+}
+
 // Dispatch (integrand, dtype, division mode) to a template instantiation. Transcendental
 // integrands (sin/cos) and the table ignore the division mode (no division in them).
 template <template <DivMode, class> class Op, class... A>
 void dispatch(const RiemannParams& p, DType dtype, DivMode m, A&&... a) {
   const Integrand f = static_cast<Integrand>(p.integrand);
+  // an explicit long tile is refused wherever the launch would not run it (any integrand,
+  // dtype or division), and a tile word out of range everywhere
+  if (p.tile != kTileAuto && p.tile != kTileShort) (void)pi4_tile_long(p, dtype, m, nullptr);
   if (dtype == DType::kF32Acc32) {
     MIINT_CHECK(f == Integrand::kPi4, "fp32 accumulation (fp32acc) is implemented for pi4 only");
     if (m == DivMode::kSeries) Op<DivMode::kSeries, Pi4F32Acc32>::run(a...);
@@ -1390,6 +1452,8 @@ void dispatch(const RiemannParams& p, DType dtype, DivMode m, A&&... a) {
   switch (f) {
     case Integrand::kPi4:
       if (m == DivMode::kSeries) Op<DivMode::kSeries, Pi4>::run(a...);
+      else if (m == DivMode::kSeriesExact && pi4_long(p, dtype, m))
+        Op<DivMode::kSeriesExact, Pi4Long>::run(a...);
       else if (m == DivMode::kSeriesExact) Op<DivMode::kSeriesExact, Pi4>::run(a...);
       else if (m == DivMode::kSeriesDirect) Op<DivMode::kSeriesDirect, Pi4>::run(a...);
       else if (pi4_narrow(p)) Op<DivMode::kIeee, Pi4>::run(a...);
@@ -1725,6 +1789,15 @@ void launch_pi4_recip_narrow(const double* d, uint64_t n, double* out, hipStream
   const uint64_t blocks = (n + B - 1) / B;
   const int grid = static_cast<int>(blocks < 8192 ? blocks : 8192);
   recip_narrow_kernel<<<grid, B, 0, stream>>>(d, n, out);
+  MIINT_HIP(hipGetLastError());
+}
+
+void launch_pk_modifier_check(const float* ac, uint64_t n, float ka, float kb, float* out,
+                              hipStream_t stream) {
+  if (n == 0) return;
+  MIINT_CHECK(n <= (uint64_t(1) << 24), "modifier check: at most 2^24 elements");
+  const int grid = static_cast<int>((n + B - 1) / B);
+  pk_modifier_check_kernel<<<grid, B, 0, stream>>>(ac, n, ka, kb, out);
   MIINT_HIP(hipGetLastError());
 }
 

@@ -36,7 +36,8 @@ T* ptr(uintptr_t p) { return reinterpret_cast<T*>(p); }
 hipStream_t stream(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 RiemannParams make_params(int integrand, double a, double h, double off, uint64_t i_begin,
-                          uint64_t n, const std::vector<double>& coef, double p0, double p1) {
+                          uint64_t n, const std::vector<double>& coef, double p0, double p1,
+                          const std::string& tile = "auto") {
   RiemannParams p{};
   p.a = a;
   p.h = h;
@@ -49,6 +50,7 @@ RiemannParams make_params(int integrand, double a, double h, double off, uint64_
   for (size_t i = 0; i < coef.size(); ++i) p.coef[i] = coef[i];
   p.p0 = p0;
   p.p1 = p1;
+  p.tile = tile_form_of(tile);
   return p;
 }
 
@@ -295,6 +297,7 @@ PYBIND11_MODULE(_miint, m) {
       .def_readwrite("host_direct", &RiemannConfig::host_direct)
       .def_readwrite("close", &RiemannConfig::close)
       .def_readwrite("work", &RiemannConfig::work)
+      .def_readwrite("tile", &RiemannConfig::tile)
       .def_readwrite("queue_wg_per_cu", &RiemannConfig::queue_wg_per_cu)
       .def_readwrite("allreduce_to_host", &RiemannConfig::allreduce_to_host)
       .def_readwrite("chain", &RiemannConfig::chain);
@@ -422,6 +425,7 @@ PYBIND11_MODULE(_miint, m) {
       .def_property_readonly("multistep", &RiemannPlan::multistep)
       .def_property_readonly("close_in_launch", &RiemannPlan::close_in_launch)
       .def_property_readonly("work", [](const RiemannPlan& p) { return std::string(p.work()); })
+      .def_property_readonly("tile", [](const RiemannPlan& p) { return std::string(p.tile()); })
       .def_property_readonly("queue_workgroups", &RiemannPlan::queue_workgroups)
       .def_property_readonly("allreduce_to_host", &RiemannPlan::allreduce_to_host)
       .def_property_readonly("direct", &RiemannPlan::direct)
@@ -434,14 +438,24 @@ PYBIND11_MODULE(_miint, m) {
       .def("device_result", [](const RiemannPlan& p, int slot) { return reinterpret_cast<uintptr_t>(p.device_result(slot)); });
 
   // ------------------------------------------------------------------ raw kernels
+  // (each raw launcher also takes a trailing `tile`: "auto" | "short" | "long", the tile form
+  // of the fp64 series_exact pi4 kernels, RiemannParams::tile)
+  auto partials_fn = [](int integrand, double a, double h, double off, uint64_t i_begin,
+                        uint64_t n, std::vector<double> coef, double p0, double p1, DType dtype,
+                        DivMode div, int grid, uintptr_t table, int table_n, uintptr_t partials,
+                        uintptr_t s, const std::string& tile) {
+    const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1, tile);
+    launch_riemann_partials(p, dtype, div, {grid, kRiemannBlock}, ptr<const double>(table),
+                            table_n, ptr<double>(partials), stream(s));
+  };
   m.def("launch_riemann_partials",
-        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
-           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div, int grid,
-           uintptr_t table, int table_n, uintptr_t partials, uintptr_t s) {
-          const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1);
-          launch_riemann_partials(p, dtype, div, {grid, kRiemannBlock}, ptr<const double>(table),
-                                  table_n, ptr<double>(partials), stream(s));
+        [partials_fn](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+                      std::vector<double> coef, double p0, double p1, DType dtype, DivMode div,
+                      int grid, uintptr_t table, int table_n, uintptr_t partials, uintptr_t s) {
+          partials_fn(integrand, a, h, off, i_begin, n, coef, p0, p1, dtype, div, grid, table,
+                      table_n, partials, s, "auto");
         });
+  m.def("launch_riemann_partials", partials_fn);
   // read-only views of the dispatcher (no launch): the lane tile a launch of these parameters
   // runs, and the division it runs (far sin / train angles included)
   m.def("riemann_tile_len",
@@ -450,6 +464,15 @@ PYBIND11_MODULE(_miint, m) {
           return riemann_tile_len(make_params(integrand, a, h, off, i_begin, n, coef, p0, p1),
                                   dtype, div);
         });
+  m.def("riemann_tile_len",
+        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div,
+           const std::string& tile) {
+          return riemann_tile_len(
+              make_params(integrand, a, h, off, i_begin, n, coef, p0, p1, tile), dtype, div);
+        });
+  m.attr("PI4_LONG_TILE") = kSeriesHalfSpanLong * 2;
+  m.def("series_ok_long", &series_ok_long);
   m.def("riemann_effective_div",
         [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
            std::vector<double> coef, double p0, double p1, DType dtype, DivMode div) {
@@ -480,27 +503,47 @@ PYBIND11_MODULE(_miint, m) {
   m.attr("FAST_TRIG_MAX_N") = kFastTrigMaxN;
   m.attr("PI4_SERIES_MAX_X") = kPi4SeriesMaxX;
   m.attr("PI4_F32_SERIES_MAX_X") = kPi4SeriesMaxXF32;
+  auto fused_fn = [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+                     std::vector<double> coef, double p0, double p1, DType dtype, DivMode div,
+                     int grid, uintptr_t table, int table_n, uintptr_t partials, uintptr_t ticket,
+                     double scale, uintptr_t out, uintptr_t s, const std::string& tile) {
+    const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1, tile);
+    launch_riemann_fused(p, dtype, div, {grid, kRiemannBlock}, ptr<const double>(table), table_n,
+                         ptr<double>(partials), ptr<unsigned>(ticket), scale, ptr<double>(out),
+                         stream(s));
+  };
   m.def("launch_riemann_fused",
-        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
-           std::vector<double> coef, double p0, double p1, DType dtype, DivMode div, int grid,
-           uintptr_t table, int table_n, uintptr_t partials, uintptr_t ticket, double scale,
-           uintptr_t out, uintptr_t s) {
-          const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1);
-          launch_riemann_fused(p, dtype, div, {grid, kRiemannBlock}, ptr<const double>(table),
-                               table_n, ptr<double>(partials), ptr<unsigned>(ticket), scale,
-                               ptr<double>(out), stream(s));
+        [fused_fn](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+                   std::vector<double> coef, double p0, double p1, DType dtype, DivMode div,
+                   int grid, uintptr_t table, int table_n, uintptr_t partials, uintptr_t ticket,
+                   double scale, uintptr_t out, uintptr_t s) {
+          fused_fn(integrand, a, h, off, i_begin, n, coef, p0, p1, dtype, div, grid, table,
+                   table_n, partials, ticket, scale, out, s, "auto");
         });
+  m.def("launch_riemann_fused", fused_fn);
+  auto points_fn = [](int integrand, double a, double h, double off, uint64_t i_begin,
+                      uint64_t n, std::vector<double> coef, double p0, double p1, DivMode div,
+                      uintptr_t table, int table_n, uintptr_t out, uintptr_t s,
+                      const std::string& tile) {
+    const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1, tile);
+    launch_riemann_point_values(p, div, ptr<const double>(table), table_n, ptr<double>(out),
+                                stream(s));
+  };
   m.def("launch_riemann_point_values",
-        [](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
-           std::vector<double> coef, double p0, double p1, DivMode div, uintptr_t table,
-           int table_n, uintptr_t out, uintptr_t s) {
-          const RiemannParams p = make_params(integrand, a, h, off, i_begin, n, coef, p0, p1);
-          launch_riemann_point_values(p, div, ptr<const double>(table), table_n, ptr<double>(out),
-                                      stream(s));
+        [points_fn](int integrand, double a, double h, double off, uint64_t i_begin, uint64_t n,
+                    std::vector<double> coef, double p0, double p1, DivMode div, uintptr_t table,
+                    int table_n, uintptr_t out, uintptr_t s) {
+          points_fn(integrand, a, h, off, i_begin, n, coef, p0, p1, div, table, table_n, out, s,
+                    "auto");
         });
+  m.def("launch_riemann_point_values", points_fn);
   m.def("launch_pi4_recip_narrow", [](uintptr_t d, uint64_t n, uintptr_t out, uintptr_t s) {
     launch_pi4_recip_narrow(ptr<const double>(d), n, ptr<double>(out), stream(s));
   });
+  m.def("launch_pk_modifier_check",
+        [](uintptr_t ac, uint64_t n, float ka, float kb, uintptr_t out, uintptr_t s) {
+          launch_pk_modifier_check(ptr<const float>(ac), n, ka, kb, ptr<float>(out), stream(s));
+        });
   m.def("launch_pi4_recip_narrow_f32", [](uintptr_t d, uint64_t n, uintptr_t out, uintptr_t s) {
     launch_pi4_recip_narrow_f32(ptr<const float>(d), n, ptr<float>(out), stream(s));
   });

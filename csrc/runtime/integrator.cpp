@@ -52,6 +52,10 @@ RiemannPlan::RiemannPlan(const RiemannConfig& cfg, int device, const Comm* comm)
   for (size_t i = 0; i < cfg.coef.size(); ++i) params_.coef[i] = cfg.coef[i];
   params_.p0 = cfg.p0;
   params_.p1 = cfg.p1;
+  params_.tile = tile_form_of(cfg.tile);
+  long_tile_ = pi4_tile_long(params_, cfg.dtype, miint::effective_div(params_, cfg.div, cfg.dtype),
+                             std::getenv("MIINT_PI4_TILE"), kPi4LongTileAuto);
+  params_.tile = long_tile_ ? kTileLong : kTileShort;  // every launcher of the plan: this form
   scale_ = params_.h * integrand_scale(cfg.integrand);
 
   const DeviceInfo info = device_info(device);
@@ -74,10 +78,15 @@ RiemannPlan::RiemannPlan(const RiemannConfig& cfg, int device, const Comm* comm)
   // 1e7: 6.0 -> 5.1 us; profiles/r1/small_n_grid.jsonl). N >= 2.7e8 keeps the full grid.
   // The grid is also rounded down to a whole number of workgroups per CU: at 275 workgroups
   // on 256 CUs, 19 CUs hold two and finish last (pi4 at 1e8: 17.9 us against 11.2 at 256).
+  // The long series_exact tile (1536 samples) counts this rule in the 384-sample tiles the
+  // same launch would otherwise run: its plans keep the grids they had (N = 1e9: the
+  // residency), and with them the queue's items and the steps' partials.
   if (cfg.grid <= 0) {
     const uint64_t cus = static_cast<uint64_t>(info.num_cus);
+    const uint64_t tl4 = long_tile_ ? std::min<uint64_t>(tl, 2 * kSeriesHalfSpan) : tl;
+    const uint64_t tiles4 = (params_.n + tl4 - 1) / tl4;
     const uint64_t four =
-        std::max<uint64_t>(cus, (tiles + 4 * bs - 1) / (4 * bs));
+        std::max<uint64_t>(cus, (tiles4 + 4 * bs - 1) / (4 * bs));
     uint64_t g = std::min<uint64_t>(static_cast<uint64_t>(shape_.grid), four);
     if (g > cus) g -= g % cus;
     shape_.grid = static_cast<int>(g);

@@ -73,7 +73,7 @@ class Integrator:
                  slice_of: tuple[int, int] | None = None, step_streams: int = 0,
                  block: int = 256, multistep: bool = True, close: str = "auto",
                  allreduce_to_host: bool = True, timeout_s: float = 300.0,
-                 work: str = "auto", queue_wg_per_cu: int = 0, **spec_kw):
+                 work: str = "auto", queue_wg_per_cu: int = 0, tile: str = "auto", **spec_kw):
         spec = integrands.get(integrand, **spec_kw) if isinstance(integrand, str) else integrand
         if a is not None or b is not None:
             spec = dataclasses.replace(spec, a=spec.a if a is None else a,
@@ -122,6 +122,9 @@ class Integrator:
                 raise ValueError("work must be auto|static|queue")
             cfg.work = work  # multi-step batches dealt statically or from a work queue
             cfg.queue_wg_per_cu = queue_wg_per_cu  # its pullers per CU (0: the residency)
+            if tile not in ("auto", "short", "long"):
+                raise ValueError("tile must be auto|short|long")
+            cfg.tile = tile  # fp64 series_exact pi4: 384- or 1536-sample tiles (plan.tile)
             cfg.allreduce_to_host = allreduce_to_host  # bucketed all-reduce into pinned memory
             cfg.timeout_s = timeout_s  # collective watchdog of the plan's sync (<= 0: none)
             if slice_of is not None:  # (rank, world): that rank's share, on this device

@@ -50,8 +50,9 @@ def default_grid() -> int:
 
 def riemann_partials(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str = "fp64",
                      div: str = "series_exact", grid: int | None = None, i_begin: int = 0,
-                     n_local: int | None = None) -> torch.Tensor:
-    """Per-workgroup unscaled partial sums of f over samples [i_begin, i_begin+n_local)."""
+                     n_local: int | None = None, tile: str = "auto") -> torch.Tensor:
+    """Per-workgroup unscaled partial sums of f over samples [i_begin, i_begin+n_local).
+    ``tile``: the tile form of the fp64 series_exact pi4 kernels, auto | short | long."""
     m = native()
     dev = _device()
     grid = grid or default_grid()
@@ -64,7 +65,7 @@ def riemann_partials(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str
                               list(spec.coef), spec.p0, spec.p1, dt, dv, grid,
                               table.data_ptr() if table is not None else 0,
                               table.numel() if table is not None else 0,
-                              partials.data_ptr(), _stream())
+                              partials.data_ptr(), _stream(), tile)
     return partials
 
 
@@ -111,7 +112,8 @@ class FusedWorkspace:
 def riemann(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str = "fp64",
             div: str = "series_exact", grid: int | None = None, i_begin: int = 0,
             n_local: int | None = None, out: torch.Tensor | None = None,
-            workspace: FusedWorkspace | None = None, fused: bool = True) -> torch.Tensor:
+            workspace: FusedWorkspace | None = None, fused: bool = True,
+            tile: str = "auto") -> torch.Tensor:
     """h * scale * sum f over this launch's samples, as a 1-element fp64 device tensor."""
     m = native()
     dev = _device()
@@ -121,7 +123,7 @@ def riemann(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str = "fp64"
     scale = h * spec.scale
     out = torch.empty(1, dtype=torch.float64, device=dev) if out is None else out
     if not fused:
-        p = riemann_partials(spec, n, rule, dtype, div, grid, i_begin, n_local)
+        p = riemann_partials(spec, n, rule, dtype, div, grid, i_begin, n_local, tile)
         return finalize(p, scale, out)
     ws = workspace or FusedWorkspace(grid, dev)
     table = _table_tensor(spec, dev)
@@ -131,12 +133,13 @@ def riemann(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str = "fp64"
                            table.data_ptr() if table is not None else 0,
                            table.numel() if table is not None else 0,
                            ws.partials.data_ptr(), ws.ticket.data_ptr(), scale, out.data_ptr(),
-                           _stream())
+                           _stream(), tile)
     return out
 
 
 def point_values(spec: IntegrandSpec, n: int, rule: str = "left", div: str = "series",
-                 i_begin: int = 0, n_local: int | None = None) -> torch.Tensor:
+                 i_begin: int = 0, n_local: int | None = None,
+                 tile: str = "auto") -> torch.Tensor:
     """Every sample's f value exactly as the hot tile path computes it (validation)."""
     m = native()
     dev = _device()
@@ -148,8 +151,20 @@ def point_values(spec: IntegrandSpec, n: int, rule: str = "left", div: str = "se
                                   getattr(m.DivMode, div),
                                   table.data_ptr() if table is not None else 0,
                                   table.numel() if table is not None else 0,
-                                  out.data_ptr(), _stream())
+                                  out.data_ptr(), _stream(), tile)
     return out
+
+
+def riemann_tile_len(spec: IntegrandSpec, n: int, rule: str = "left", dtype: str = "fp64",
+                     div: str = "series_exact", i_begin: int = 0, n_local: int | None = None,
+                     tile: str = "auto") -> int:
+    """Samples per lane tile of the kernel a launch of these parameters runs (host only: a
+    read-only view of the dispatcher, no device needed)."""
+    m = native()
+    n_local = n if n_local is None else n_local
+    dt, dv = _enums(dtype, div)
+    return m.riemann_tile_len(spec.native_id, spec.a, (spec.b - spec.a) / n, _RULE_OFF[rule],
+                              i_begin, n_local, list(spec.coef), spec.p0, spec.p1, dt, dv, tile)
 
 
 def pi4_recip_narrow(d: torch.Tensor) -> torch.Tensor:
@@ -160,6 +175,20 @@ def pi4_recip_narrow(d: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(d)
     launch = native().launch_pi4_recip_narrow_f32 if f32 else native().launch_pi4_recip_narrow
     launch(d.data_ptr(), d.numel(), out.data_ptr(), _stream())
+    return out
+
+
+def pk_modifier_check(ac: torch.Tensor, ka: float, kb: float) -> torch.Tensor:
+    """The packed-fp32 source modifiers of the long pi4 tile (validation): ``ac`` is n x 4 fp32
+    (slope pair, centre pair); returns n x 16 fp32: columns 0..7 the residual pairs formed from
+    one scalar pair (ka, kb) through op_sel and neg_hi, columns 8..15 the same from (k, -k)
+    scalar pairs, in the order (ka, low), (kb, low), (ka, high), (kb, high)."""
+    _check(ac, dtype=torch.float32, name="ac")
+    if ac.dim() != 2 or ac.shape[1] != 4:
+        raise ValueError("ac must be n x 4")
+    out = torch.empty((ac.shape[0], 16), dtype=torch.float32, device=ac.device)
+    native().launch_pk_modifier_check(ac.data_ptr(), ac.shape[0], float(ka), float(kb),
+                                      out.data_ptr(), _stream())
     return out
 
 

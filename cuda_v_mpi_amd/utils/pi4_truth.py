@@ -51,6 +51,7 @@ MP.prec = 2 * PREC      # values; true_sum raises it with |w|
 SCALE = 4.0             # Pi4::kScale
 # tile lengths (asserted against the extension's riemann_tile_len in the GPU tests)
 TILE64 = 384            # Pi4::kSeriesTile: series, series_exact
+TILE64_LONG = 1536      # Pi4Long::kTile: series_exact where 768 |h| <= HALF_SPAN_H (LONG_PATH)
 TILE32 = 192            # Pi4F32::kSubs * kSubLen: fp32 and fp32acc series
 TILE_PER_SAMPLE = 32    # series_direct and every ieee tile
 HALF_SPAN_H = 2.0e-6    # kernels.hpp series_ok / series_ok_f32 / direct_ok: (T / 2) |h| <= this
@@ -76,9 +77,25 @@ SERIES_PATHS = ("fp64-series_exact", "fp64-series", "fp64-series_direct", "fp32-
                 "fp32acc-series")
 
 
+# The long series_exact tile (integrands.hpp Pi4Long; kernels.hpp pi4_tile_long): a path name of
+# its own here, the same division ("series_exact") on the device. Not in PATHS / SERIES_PATHS,
+# which enumerate the cases of the tests written before it existed.
+LONG_PATH = "fp64-series_exact-long"
+
+
+def _series(path: str) -> bool:
+    return path in SERIES_PATHS or path == LONG_PATH
+
+
+def long_tile_admitted(h: float) -> bool:
+    """kernels.hpp series_ok_long: 0 < 768 |h| <= 2e-6 (a degenerate interval keeps the short
+    tile)."""
+    return 0.0 < abs(h) and (TILE64_LONG // 2) * abs(h) <= HALF_SPAN_H
+
+
 def tile_len(path: str) -> int:
     return {"fp64-series_exact": TILE64, "fp64-series": TILE64, "fp32-series": TILE32,
-            "fp32acc-series": TILE32}.get(path, TILE_PER_SAMPLE)
+            "fp32acc-series": TILE32, LONG_PATH: TILE64_LONG}.get(path, TILE_PER_SAMPLE)
 
 
 def seed_residual(path: str) -> float:
@@ -86,7 +103,7 @@ def seed_residual(path: str) -> float:
     (seed_half, seed_exact: EM_RAW64), v_rcp_f64 and one Newton step (Pi4::seed: the step
     squares 2**-23 to 2**-46 and rounds s once, 2**-53: under 2**-45), v_rcp_f32 and one
     Newton step (EM_NEWTON32)."""
-    return {"fp64-series_exact": EM_RAW64, "fp64-series": EM_RAW64,
+    return {"fp64-series_exact": EM_RAW64, "fp64-series": EM_RAW64, LONG_PATH: EM_RAW64,
             "fp64-series_direct": 2.0 ** -45}.get(path, EM_NEWTON32)
 
 
@@ -256,7 +273,7 @@ def tile_anchor(g: Geometry, path: str, tile: int = 0) -> float:
     ib = base + tile * T + anchor, anchor = (T - 1) / 2 for the midpoint-anchored series tiles
     (Pi4::anchor, Pi4F32::anchor) and 0 otherwise. ib is an exact double (< 2**52 + T)."""
     T = tile_len(path)
-    mid = path in ("fp64-series_exact", "fp64-series", "fp32-series", "fp32acc-series")
+    mid = path in ("fp64-series_exact", "fp64-series", "fp32-series", "fp32acc-series", LONG_PATH)
     ib = base_index(g) + float(tile * T) + (0.5 * (T - 1) if mid else 0.0)
     return fma64(ib, g.h, g.a)
 
@@ -309,7 +326,7 @@ def defined_inputs(path: str, g: Geometry, tile: int = 0) -> dict:
         return {"xm": _fr(xm), "h": _fr(hf), "dm": _fr(fma32(xm, xm, np.float32(1.0)))}
     if path == "fp64-series":
         return {"xm": _fr(xa), "h": Fraction(g.h), "dm": _fr(fma64(xa, xa, 1.0))}
-    if path == "fp64-series_exact":
+    if path in ("fp64-series_exact", LONG_PATH):
         return {"xm": _fr(xa), "h": Fraction(g.h), "dm": 1 + _fr(xa) ** 2}
     raise ValueError(path)
 
@@ -574,6 +591,21 @@ def tile_defn_rel(path: str, g: Geometry) -> float:
       dropped e^3 / (1 - e)
     about 2.3e-16 on [0, 1], 2.9e-16 beyond.
 
+    fp64-series_exact-long (Pi4Long::tile_acc, T = 1536): s 1536 + s (lin + sum e_sq^2), the
+    short tile's terms with the long tile's spans (E = seed_residual + 768 |h| (1 + 768 |h|)):
+      e_m (seed_exact)      as above: 2**-54 where |x| can pass 1, 4 U64 EM_RAW64
+      lin = fma(kSumK2, B, 1536 e_m)  1536 e_m rounds (U64 E), B carries 2 U64 (h^2 kSumK2 /
+                            1536 <= (768 h)^2 / 3 per sample), the fma rounds (U64 E)
+      squares               per sample 2 E |de| + U32 E^2 with |de| <= 5 U32 E (A, B, the base
+                            e_m + 341.25 B, in, e_c, A', e: derivation above Pi4Long), and the
+                            curvature the square leaves out, 2 E 651 h^2; four fp32 lanes of 384
+                            squares of at most E^2: 4 * 384 * 384 U32 E^2 / 1536 per sample
+      t = lin + (x + y)     2 U64 E
+      fl(1536 s) and the outer fma    2 U64
+      dropped e^3 / (1 - e)
+    about 3.5e-16 at the largest admitted h on [0, 1] (the fp32 sums' worst case, 9.2e-17, is
+    what it adds to the short tile's), 2.4e-16 at N = 1e9.
+
     fp64-series_direct (Pi4::tile kSeriesDirect, 32 samples): e = fma(-d, s, 1) rounds
     (U64 E); t1a, t1b: 16 additions each of at most U64 16 E, joined (U64 32 E); t2: 32 fma of
     at most U64 32 E^2; (t1a + t1b) + t2 (U64 32 E): per sample U64 E (1 + 16 + 1 + 1) and the
@@ -594,6 +626,12 @@ def tile_defn_rel(path: str, g: Geometry) -> float:
         off_unit = 2.0 ** -54 if g.x_abs_max + 192.0 * h > 1.0 else 0.0
         rel = (off_unit + 4.0 * U64 * EM_RAW64 + 2.0 * U64 * E
                + 2.0 * U64 * (192.0 * h) ** 2 / 3.0 + 2.2e-18 + 96.0 * U32 * E * E
+               + 2.0 * U64 * E + E ** 3 / (1.0 - E)) * (1.0 + 2.0 * E) + 2.0 * U64
+    elif path == LONG_PATH:
+        off_unit = 2.0 ** -54 if g.x_abs_max + 768.0 * h > 1.0 else 0.0
+        squares = 2.0 * E * 5.0 * U32 * E + U32 * E * E + 2.0 * E * 651.0 * h * h
+        rel = (off_unit + 4.0 * U64 * EM_RAW64 + 2.0 * U64 * E
+               + 2.0 * U64 * (768.0 * h) ** 2 / 3.0 + squares + 384.0 * U32 * E * E
                + 2.0 * U64 * E + E ** 3 / (1.0 - E)) * (1.0 + 2.0 * E) + 2.0 * U64
     elif path == "fp64-series_direct":
         rel = (19.0 * U64 * E + 33.0 * U64 * E * E + E ** 3 / (1.0 - E)) * (1.0 + 2.0 * E) + U64
@@ -616,7 +654,7 @@ def defn_truth_rel(path: str, g: Geometry) -> float:
                    exact in fp32 too (`exact`-coordinate family: callers pass a geometry for
                    which float32(x_m) == x_m; see fp32_coords_exact) only the d_m term is left."""
     h = abs(g.h)
-    if path == "fp64-series_exact":
+    if path in ("fp64-series_exact", LONG_PATH):
         rel = coord_rel(g, 1)
     elif path == "fp64-series":
         rel = coord_rel(g, 1) + U64 * (1.0 + 2.0 * 192.0 * h)
@@ -668,7 +706,7 @@ def tile_truth_bound(path: str, g: Geometry, true_tile_sum: float) -> float:
     exact)."""
     S = abs(true_tile_sum)
     T = tile_len(path)
-    if path in SERIES_PATHS:
+    if _series(path):
         rel = tile_defn_rel(path, g) + defn_truth_rel(path, g)
     elif path == "fp64-ieee":
         rel = ieee_rel(path, g) + 32.0 * U64
@@ -707,7 +745,7 @@ def launch_sum_bound(path: str, g: Geometry, true_total: float, grid: int, block
     every sample adds underflow_floor."""
     T = tile_len(path)
     S = abs(true_total)
-    if path in SERIES_PATHS:
+    if _series(path):
         rel = tile_defn_rel(path, g) + defn_truth_rel(path, g)
     elif path == "fp64-ieee":
         rel = ieee_rel(path, g) + 32.0 * U64

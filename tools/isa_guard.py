@@ -79,6 +79,11 @@ GUARDED = {
     "q_table_series": ("riemann", QK + r"0ENS_5TableEEEv", 0),
     "q_table_ieee": ("riemann", QK + r"1ENS_5TableEEEv", 0),
     "qt_pi4_series_exact": ("riemann", QT + r"3ENS_3Pi4EEEv", 0),
+    # the 1536-sample series_exact tile (integrands.hpp Pi4Long; fine steps): the one-step,
+    # multi-step and queue kernels, each at no less than its Pi4 row's occupancy
+    "pi4_series_exact_long": ("riemann", CH + r"3ENS_7Pi4LongEE", 1536),
+    "ms_pi4_series_exact_long": ("riemann", MS + r"3ENS_7Pi4LongELb0EE", 0),
+    "q_pi4_series_exact_long": ("riemann", QK + r"3ENS_7Pi4LongEEEv", 0),
     "table2d_stream_0_16": ("table", r"table2d_stream_kernelILi0ELi16ELb0EE", 0),
     "table2d_stream_0_30": ("table", r"table2d_stream_kernelILi0ELi30ELb0EE", 0),
     "table2d_stream_1_16": ("table", r"table2d_stream_kernelILi1ELi16ELb0EE", 0),
