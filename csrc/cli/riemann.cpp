@@ -32,7 +32,10 @@
 // every sample, or every --every K-th one, to --running-out FILE (raw fp64) or as "x value"
 // lines; one rank. With --ya AY --yb BY the expression is over x and y and its double integral
 // on [a, b] x [ya, yb] is taken with --n x --ny samples (ExprIntegrator2D, HostExpr2D), the
-// ranks splitting the sample rows.
+// ranks splitting the sample rows. With --rtol R and / or --atol T the expression is integrated
+// to that tolerance (ExprAdaptive: Gauss-Kronrod (7, 15), bisection where the estimate misses):
+// the value, or with --json every field of the result; a warning on stderr when not converged.
+// One GPU, one rank: no sample count, rule, sweep, curve, y range or host engine goes with it.
 //
 //   ./riemann [--n 1e9] [--gpus G] [--integrand sin|pi4|poly|train] [--rule left|mid|right]
 //             [--dtype fp64|fp32|fp32acc] [--iters K] [--block 64..1024] [--grid G] [--parity]
@@ -41,6 +44,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -461,8 +465,88 @@ int run_expr2d(const cli::Args& a, const RiemannConfig& cfg, double nd, int iter
   return 0;
 }
 
+// --expr with --rtol / --atol: the integral to a tolerance (ExprAdaptive). One GPU, one rank.
+// A number that does not parse, or a flag of another mode, is refused before any device call.
+bool adaptive_requested(const cli::Args& a) { return a.has("rtol") || a.has("atol"); }
+
+double adaptive_number(const cli::Args& a, const std::string& key, double dflt, bool whole) {
+  if (!a.has(key)) return dflt;
+  const std::string text = a.str(key, "");
+  char* end = nullptr;
+  const double v = std::strtod(text.c_str(), &end);
+  MIINT_CHECK(end != text.c_str() && *end == '\0' && std::isfinite(v) &&
+                  (!whole || (v == std::floor(v) && std::fabs(v) < 9.0e15)),
+              "--" + key + " must be " + (whole ? "a whole number" : "a number") + " (got '" +
+                  text + "')");
+  return v;
+}
+
+int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
+  for (const char* k : {"n", "rule", "running", "ya", "yb", "ny", "params", "linspace", "every",
+                        "running-out", "loopback"})
+    MIINT_CHECK(!a.has(k), std::string("--rtol / --atol choose the samples themselves: --") + k +
+                               " does not go with them");
+  MIINT_CHECK(a.integer("gpus", 1) <= 1, "--rtol / --atol run on one GPU: --gpus " +
+                                             a.str("gpus", "") + " does not go with them (the "
+                                             "tolerance would need a collective every round)");
+  MIINT_CHECK(cli::env_int("WORLD_SIZE", 1) <= 1,
+              "--rtol / --atol run as one rank: a rank environment (WORLD_SIZE = " +
+                  std::to_string(cli::env_int("WORLD_SIZE", 1)) + ") does not go with them");
+  MIINT_CHECK(!cli::on_cpu(a), "--rtol / --atol have no host engine: --device cpu does not go "
+                               "with them");
+  AdaptOptions o;
+  o.rtol = adaptive_number(a, "rtol", o.rtol, false);
+  o.atol = adaptive_number(a, "atol", 0.0, false);
+  const double panels = adaptive_number(a, "panels", static_cast<double>(o.panels), true);
+  const double depth = adaptive_number(a, "max-depth", o.max_depth, true);
+  const double max_iv = adaptive_number(a, "max-intervals", static_cast<double>(o.max_intervals), true);
+  MIINT_CHECK(panels >= 0 && max_iv >= 0 && std::fabs(depth) < 1e9,
+              "--panels, --max-intervals and --max-depth must not be negative or huge");
+  o.panels = static_cast<uint64_t>(panels);
+  o.max_depth = static_cast<int>(depth);
+  o.max_intervals = static_cast<uint64_t>(max_iv);
+  adapt_check(cfg.a, cfg.b, o);
+  const std::string expr = a.str("expr", "");
+  (void)expr_adapt_source(expr);  // a rejected expression: before any device call
+  MIINT_CHECK(device_count() >= 1, "--rtol / --atol need a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprAdaptive ea(expr, 0);
+  const AdaptResult r = ea.integrate(cfg.a, cfg.b, o);
+  const double secs = wall_seconds() - process_start_seconds();
+  if (!r.converged)
+    std::fprintf(stderr, "riemann: not converged: err_est %.3g against tol %.3g (capped %d, "
+                 "nonfinite %llu, forced %llu)\n", r.err_est, r.tol, r.capped ? 1 : 0,
+                 static_cast<unsigned long long>(r.nonfinite),
+                 static_cast<unsigned long long>(r.forced));
+  if (!a.flag("json")) std::printf("%.17g\n", r.value);
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
+      .add("rtol", o.rtol).add("atol", o.atol).add("panels", static_cast<double>(o.panels))
+      .add("max_depth", o.max_depth).add("max_intervals", static_cast<double>(o.max_intervals))
+      .add("value", r.value).add("err_est", r.err_est).add("resabs", r.resabs).add("tol", r.tol)
+      .add("converged", r.converged).add("evals", static_cast<double>(r.evals))
+      .add("rounds", static_cast<double>(r.rounds))
+      .add("intervals", static_cast<double>(r.intervals))
+      .add("splits", static_cast<double>(r.splits)).add("floor", static_cast<double>(r.floor))
+      .add("forced", static_cast<double>(r.forced))
+      .add("nonfinite", static_cast<double>(r.nonfinite)).add("capped", r.capped);
+  // %.17g round-trips a finite value; a non-finite one prints as null, its bits are here
+  char bits[24];
+  uint64_t w = 0;
+  std::memcpy(&w, &r.value, sizeof w);
+  std::snprintf(bits, sizeof bits, "%016llx", static_cast<unsigned long long>(w));
+  rec.add("value_bits", bits);
+  if (a.has("analytic")) {
+    const double exact = a.num("analytic", 0.0);
+    rec.add("analytic", exact).add("abs_err", std::fabs(r.value - exact));
+  }
+  cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (adaptive_requested(a)) return run_expr_adaptive(a, cfg);
   if (a.has("ya")) return run_expr2d(a, cfg, nd, iters);
   if (a.flag("running")) return run_expr_running(a, cfg, nd);
   if (a.has("params") || a.has("linspace")) return run_expr_sweep(a, cfg, nd, iters);
@@ -524,6 +608,8 @@ constexpr const char* kUsage =
     "               [--expr EXPR --params FILE | --linspace p0=LO:HI:COUNT]\n"
     "               [--expr EXPR --a A --b B --n N --running [--every K] [--running-out FILE]]\n"
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
+    "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
+    "                [--max-intervals M]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
     "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n"
     "--running: the running integral F(x) = h * sum of f up to x at every sample (one GPU,\n"
@@ -533,7 +619,14 @@ constexpr const char* kUsage =
     "--ya AY --yb BY: the double integral of --expr over x and y on [AX, BX] x [AY, BY], NX x NY\n"
     "  samples (--ny defaults to --n), the same rule on both axes; ranks split the sample rows\n"
     "  (--gpus, --loopback, rank environment, --device cpu [--threads T] as for --expr);\n"
-    "  --json: expr, a, b, ya, yb, n, ny, rule, value, device_ms, samples_per_s.\n";
+    "  --json: expr, a, b, ya, yb, n, ny, rule, value, device_ms, samples_per_s.\n"
+    "--rtol R / --atol T: the integral of --expr on [A, B] to the tolerance max(T, R |value|)\n"
+    "  (adaptive Gauss-Kronrod (7, 15) from --panels P equal intervals, default 65536, bisected at\n"
+    "  most --max-depth D times, default 60, at most --max-intervals M in all, default 2^22);\n"
+    "  prints the value, and a warning on stderr when not converged; --json: value, err_est,\n"
+    "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
+    "  device_ms. One GPU, one rank, no host engine: refused with --n, --rule, --running, --ya,\n"
+    "  --params, --linspace, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n";
 
 int main(int argc, char** argv) {
   try {
@@ -587,6 +680,11 @@ int main(int argc, char** argv) {
                 "--ny belongs to a double integral (--ya AY --yb BY)");
     MIINT_CHECK(a.has("expr") || !a.has("ya"),
                 "--ya / --yb are the double integral of an --expr integrand over x and y");
+    MIINT_CHECK(a.has("expr") || !adaptive_requested(a),
+                "--rtol / --atol are the tolerance of an --expr integrand");
+    MIINT_CHECK(adaptive_requested(a) ||
+                    !(a.has("panels") || a.has("max-depth") || a.has("max-intervals")),
+                "--panels / --max-depth / --max-intervals belong to --rtol / --atol");
     if (a.has("expr")) return run_expr(a, cfg, nd, iters);
     if (cli::on_cpu(a)) return run_host(a, cfg, nd, iters);
     const cli::Topology topo = cli::topology(a);

@@ -361,4 +361,121 @@ class ExprIntegrator2D {
   detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
+// ---------------------------------------------------------------------------------------
+// Adaptive integration: the integral of f(x) on [a, b] to a requested tolerance, with an error
+// estimate and a `converged` flag, the samples placed where the integrand needs them.
+//
+// Every family above sums n equally spaced samples and leaves n to the caller. Here the
+// Gauss-Kronrod (7, 15) pair is applied to a list of intervals, and the intervals whose
+// estimate misses their share of the tolerance are bisected, round by round (expr_adaptive.cpp).
+// On [lo, hi] with hw = 0.5 (hi - lo), c = lo + hw and nodes x_j = fma(hw, t_j, c):
+//   K = hw sum wk_j f(x_j) (15 nodes), G = hw sum wg_j f(x_j) (the 7 Gauss nodes among them),
+//   R = hw sum wk_j |f(x_j)|, err = |K - G|. Neither endpoint is evaluated.
+// The list starts as `panels` equal intervals (edges a + ((b - a) k) / panels, the last one b)
+// and stays in x order. A round, over the whole active list of n intervals:
+//
+//   miint_adapt_eval     one interval per lane: K, err, R; one partial of K per workgroup
+//   miint_adapt_close    one workgroup: sum_K in index order, t = rtol |S_acc + sum_K|,
+//                        tol = atol > t ? atol : t (a NaN sum gives a NaN tolerance)
+//   miint_adapt_decide   per interval, in this order: K or err not finite -> accept, counted
+//                        in `nonfinite`; not (err > (tol w) / W), w = hi - lo, W = |b - a| ->
+//                        accept (so a NaN tolerance accepts everything: the value is lost
+//                        already); err <= 50 * 2^-52 R -> accept, counted in `floor` (rounding
+//                        noise: bisection cannot improve it); depth >= max_depth, or c equal
+//                        to lo or hi -> accept, counted in `forced`; else split. Per
+//                        workgroup: the split count, the counters, the sums of the accepted
+//                        K, err, R and of the K and err to be split
+//   miint_adapt_prefix   one workgroup: exclusive prefix of the split counts, the round's sums
+//                        in workgroup order onto S_acc, E_acc, R_acc, the round's record
+//                        into pinned host memory. When the partition (the intervals accepted
+//                        so far plus the next list) would pass max_intervals the round is
+//                        `capped`: nothing is split, the pending K and err join the totals
+//   miint_adapt_scatter  the children (lo, c), (c, hi) at depth + 1 take their parent's place in
+//                        the other list (2 * exclusive prefix); the accepted intervals go to
+//                        the caller's buffer if one was given
+//
+// The host reads the record (the next count and the flags) after one sync per round and stops
+// when the next list is empty or the round was capped. No workgroup waits on another, the launch
+// shapes depend on the active count only and every sum has a fixed order: bitwise reproducible.
+// a > b integrates [b, a] and negates the value; a == b gives 0 with no launch. The partition
+// never passes max_intervals, so a caller's interval buffer of that capacity cannot overflow.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t kAdaptMaxIntervalsLimit = 1ull << 26;  // the lists alone are 2 GB there
+constexpr int kAdaptMaxDepthLimit = 200;
+
+// The one table of the rule. gk15_nodes(): the 15 Kronrod nodes on [-1, 1], ascending;
+// gk15_weights(): their weights; gk7_weights(): the weights of the 7 Gauss nodes, which are
+// nodes 1, 3, ..., 13. The generated source prints the same doubles as hex floats.
+std::vector<double> gk15_nodes();
+std::vector<double> gk15_weights();
+std::vector<double> gk7_weights();
+// The 15 nodes fma(hw, t_j, c) of [lo, hi], ascending: the bits the kernels evaluate f at.
+void gk15_abscissae(double lo, double hi, double* x15);
+
+// The panels a call starts from unless told. A round costs about 28 us whatever it holds (five
+// launches and a sync) and 983040 evaluations cost what 3840 do, so starting fine saves rounds:
+// against 256 and 4096, 65536 took 0.034 instead of 0.25 and 0.15 ms for 1.0/(x*x+1e-8) and
+// the same time for exp(-x*x) and 1.0/sqrt(x) (profiles/r21/expr_adaptive.md).
+constexpr uint64_t kAdaptDefaultPanels = 65536;
+
+struct AdaptOptions {
+  double rtol = 1e-10, atol = 0.0;
+  uint64_t panels = kAdaptDefaultPanels;
+  int max_depth = 60;
+  uint64_t max_intervals = 1ull << 22;
+};
+struct AdaptResult {
+  double value = 0.0, err_est = 0.0, resabs = 0.0;
+  double tol = 0.0;            // the last round's tolerance
+  bool converged = false;      // err_est <= tol, not capped, nonfinite == 0
+  uint64_t evals = 0;          // 15 x intervals evaluated
+  uint64_t rounds = 0, intervals = 0, splits = 0;
+  uint64_t floor = 0, forced = 0, nonfinite = 0;
+  bool capped = false;
+  double device_ms = 0.0;      // events around the call's rounds
+};
+
+// Throws, naming the numbers, unless a and b are finite, rtol and atol are >= 0 and not both
+// 0, 1 <= max_intervals <= 2^26, 1 <= panels <= max_intervals and 0 <= max_depth <= 200. No
+// device needed; nothing is launched after a refusal.
+void adapt_check(double a, double b, const AdaptOptions& opt);
+std::string expr_adapt_source(const std::string& expr);
+// hipRTC compile for gfx950 (no device needed), cached per expression.
+std::string expr_adapt_compile(const std::string& expr);
+
+class ExprAdaptive {
+ public:
+  ExprAdaptive(const std::string& expr, int device = 0);
+  ExprAdaptive(const ExprAdaptive&) = delete;
+  ExprAdaptive& operator=(const ExprAdaptive&) = delete;
+  // The integral of f on [a, b] by the rounds above. With intervals_out (device memory,
+  // `capacity` pairs of doubles; refused up front unless capacity >= max_intervals) the final
+  // partition is also stored there as (lo, hi) pairs running from a to b: result.intervals
+  // of them. Synchronous: one sync per round.
+  AdaptResult integrate(double a, double b, const AdaptOptions& opt = {},
+                        double* intervals_out = nullptr, uint64_t capacity = 0);
+  // Device ms per call over `iters` back-to-back calls (events around them; the rounds' syncs
+  // and the host's reads between them are inside).
+  double time(double a, double b, const AdaptOptions& opt, int iters);
+  const std::string& expression() const { return expr_; }
+
+ private:
+  void reserve(uint64_t max_intervals);
+  AdaptResult rounds(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t cap);
+  std::string expr_;
+  int device_;
+  Stream stream_;
+  uint64_t reserved_ = 0;
+  DeviceBuffer<double> list_[2];        // (lo, hi) pairs: 2 x max_intervals doubles each
+  DeviceBuffer<unsigned> depth_[2];
+  DeviceBuffer<double> k_, err_, r_;    // per interval
+  DeviceBuffer<unsigned char> split_;   // per interval: 1 = bisect
+  DeviceBuffer<double> part_k_, blk_sums_;  // per workgroup: 1 and 5 doubles
+  DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 4 counters; the split prefix
+  DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive.cpp)
+  PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
+  Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+};
+
 }  // namespace miint

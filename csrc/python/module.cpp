@@ -996,6 +996,105 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprIntegrator2D::expression);
 
+  // adaptive integration: Gauss-Kronrod (7, 15), bisection by rounds, to a tolerance
+  m.attr("ADAPT_MAX_INTERVALS_LIMIT") = kAdaptMaxIntervalsLimit;
+  m.attr("ADAPT_MAX_DEPTH_LIMIT") = kAdaptMaxDepthLimit;
+  m.attr("ADAPT_DEFAULT_PANELS") = kAdaptDefaultPanels;
+  auto as_array = [](const std::vector<double>& v) {
+    return py::array_t<double>(static_cast<py::ssize_t>(v.size()), v.data());
+  };
+  m.def("gk15_nodes", [as_array] { return as_array(gk15_nodes()); },
+        "the 15 Kronrod nodes on [-1, 1], ascending (the rule's own table)");
+  m.def("gk15_weights", [as_array] { return as_array(gk15_weights()); },
+        "the weights of gk15_nodes()");
+  m.def("gk7_weights", [as_array] { return as_array(gk7_weights()); },
+        "the weights of the 7 Gauss nodes, which are nodes 1, 3, ..., 13 of gk15_nodes()");
+  m.def("gk15_abscissae",
+        [](py::array_t<double, py::array::c_style | py::array::forcecast> lo,
+           py::array_t<double, py::array::c_style | py::array::forcecast> hi) {
+          MIINT_CHECK(lo.ndim() == 1 && hi.ndim() == 1 && lo.shape(0) == hi.shape(0),
+                      "gk15_abscissae: lo and hi are 1-D arrays of one length");
+          const py::ssize_t n = lo.shape(0);
+          py::array_t<double> out({n, py::ssize_t(15)});
+          for (py::ssize_t i = 0; i < n; ++i)
+            gk15_abscissae(lo.data()[i], hi.data()[i], out.mutable_data() + 15 * i);
+          return out;
+        },
+        py::arg("lo"), py::arg("hi"),
+        "the nodes fma(hw, t_j, c) of every interval [lo_i, hi_i] as an n x 15 array: the bits "
+        "the adaptive kernels evaluate f at");
+  py::class_<AdaptOptions>(m, "AdaptOptions", "tolerances and bounds of an adaptive integration")
+      .def(py::init([](double rtol, double atol, uint64_t panels, int max_depth,
+                       uint64_t max_intervals) {
+             AdaptOptions o;
+             o.rtol = rtol;
+             o.atol = atol;
+             o.panels = panels;
+             o.max_depth = max_depth;
+             o.max_intervals = max_intervals;
+             return o;
+           }),
+           py::arg("rtol") = 1e-10, py::arg("atol") = 0.0, py::arg("panels") = kAdaptDefaultPanels,
+           py::arg("max_depth") = 60, py::arg("max_intervals") = uint64_t(1) << 22)
+      .def_readwrite("rtol", &AdaptOptions::rtol)
+      .def_readwrite("atol", &AdaptOptions::atol)
+      .def_readwrite("panels", &AdaptOptions::panels)
+      .def_readwrite("max_depth", &AdaptOptions::max_depth)
+      .def_readwrite("max_intervals", &AdaptOptions::max_intervals);
+  py::class_<AdaptResult>(m, "AdaptResult", "value, error estimate and counters of one call")
+      .def_readonly("value", &AdaptResult::value)
+      .def_readonly("err_est", &AdaptResult::err_est)
+      .def_readonly("resabs", &AdaptResult::resabs)
+      .def_readonly("tol", &AdaptResult::tol)
+      .def_readonly("converged", &AdaptResult::converged)
+      .def_readonly("evals", &AdaptResult::evals)
+      .def_readonly("rounds", &AdaptResult::rounds)
+      .def_readonly("intervals", &AdaptResult::intervals)
+      .def_readonly("splits", &AdaptResult::splits)
+      .def_readonly("floor", &AdaptResult::floor)
+      .def_readonly("forced", &AdaptResult::forced)
+      .def_readonly("nonfinite", &AdaptResult::nonfinite)
+      .def_readonly("capped", &AdaptResult::capped)
+      .def_readonly("device_ms", &AdaptResult::device_ms)
+      .def("as_dict", [](const AdaptResult& r) {
+        py::dict d;
+        d["value"] = r.value;
+        d["err_est"] = r.err_est;
+        d["resabs"] = r.resabs;
+        d["tol"] = r.tol;
+        d["converged"] = r.converged;
+        d["evals"] = r.evals;
+        d["rounds"] = r.rounds;
+        d["intervals"] = r.intervals;
+        d["splits"] = r.splits;
+        d["floor"] = r.floor;
+        d["forced"] = r.forced;
+        d["nonfinite"] = r.nonfinite;
+        d["capped"] = r.capped;
+        d["device_ms"] = r.device_ms;
+        return d;
+      });
+  m.def("adapt_check", &adapt_check, py::arg("a"), py::arg("b"), py::arg("options"),
+        "raise, naming the numbers, unless the range and the options are ones ExprAdaptive takes");
+  m.def("expr_adapt_source", &expr_adapt_source, py::arg("expr"),
+        "source of the adaptive kernels generated for an expression over x");
+  m.def("expr_adapt_compile", compiled(&expr_adapt_compile), py::arg("expr"),
+        "compile the adaptive kernels for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprAdaptive>(m, "ExprAdaptive",
+                           "the integral of f(x) to a requested tolerance (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("device") = 0)
+      .def("integrate",
+           [](ExprAdaptive& e, double a, double b, const AdaptOptions& o, uintptr_t out,
+              uint64_t capacity) {
+             return e.integrate(a, b, o, reinterpret_cast<double*>(out), capacity);
+           },
+           py::arg("a"), py::arg("b"), py::arg("options") = AdaptOptions(),
+           py::arg("intervals_out") = 0, py::arg("capacity") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("time", &ExprAdaptive::time, py::arg("a"), py::arg("b"), py::arg("options"),
+           py::arg("iters"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprAdaptive::expression);
+
   // ------------------------------------------------------------------ host (CPU) engine
   m.def("host_isa", &host_isa, "vector ISA the host kernels dispatch to: avx512|avx2|base");
   py::class_<HostPool>(m, "HostPool", "persistent host worker threads (0 = one per core)")

@@ -20,7 +20,10 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     every sample, or every K-th one, in one call (``integrate_expr_running``,
     ``ops.kernels.riemann_expr_scan``, ``riemann --expr ... --running``), and double
     integrals of f(x, y) over a rectangle (``integrate_expr2d``,
-    ``ops.kernels.riemann_expr2d``, ``riemann --expr ... --ya AY --yb BY``).
+    ``ops.kernels.riemann_expr2d``, ``riemann --expr ... --ya AY --yb BY``), and its
+    integral to a requested tolerance with an error estimate, the samples placed where
+    the integrand needs them (``integrate_expr_adaptive``, ``ops.kernels.quad_expr``,
+    ``riemann --expr ... --rtol R``).
 
 Layout: models/ (integrands), ops/ (kernel entry points), parallel/ (decomposition,
 process groups), utils/ (fixtures, oracles, output formats), integrate.py (high-level API).
@@ -34,4 +37,5 @@ from .integrate import IntegrationResult, Integrator, integrate, integrate_expr 
 from .integrate import SweepResult, integrate_expr_sweep  # noqa: F401
 from .integrate import RunningResult, integrate_expr_running  # noqa: F401
 from .integrate import integrate_expr2d  # noqa: F401
+from .integrate import AdaptiveResult, integrate_expr_adaptive  # noqa: F401
 from .models import integrands  # noqa: F401

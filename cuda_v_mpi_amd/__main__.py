@@ -8,6 +8,7 @@ SURVEY §2.6) on top of the Python API, and adds JSON output:
     trainscan   two-phase prefix scan (4main.c)                   [--parity --algo lookback]
     integrate   any integrand, JSON result                        [--integrand --n --rule ...]
                 or any f(x):  --expr "exp(-x*x)" --a 0 --b 3 (compiled at run time, hipRTC)
+                or to a tolerance: --expr "1.0/sqrt(x)" --a 0 --b 1 --rtol 1e-10
     table2d     2-D velocity field v(x) v(y), bilinear, JSON      [--grid 4096 --iters 100]
     oracle      print every SURVEY §6.1 oracle value (CPU only)
     scale       GPU-count sweep 1,2,4,8: weak/strong efficiency, RCCL latency [--gpus 1,2,4,8]
@@ -191,6 +192,13 @@ def cmd_integrate(a) -> int:
 
         lo = 0.0 if a.a is None else a.a
         hi = 1.0 if a.b is None else a.b
+        if a.rtol is not None or a.atol is not None:
+            return _integrate_adaptive(a, lo, hi)
+        if a.panels is not None or a.max_depth is not None or a.max_intervals is not None:
+            raise SystemExit("integrate: --panels / --max-depth / --max-intervals belong to "
+                             "--rtol / --atol")
+        a.n = 1e9 if a.n is None else a.n
+        a.rule = a.rule or "left"
         if (a.ya is None) != (a.yb is None):
             raise SystemExit("integrate: --ya and --yb go together (the y interval of a double "
                              "integral)")
@@ -241,12 +249,59 @@ def cmd_integrate(a) -> int:
         print(json.dumps(rec))
         return 0
 
+    if (a.rtol is not None or a.atol is not None or a.panels is not None
+            or a.max_depth is not None or a.max_intervals is not None):
+        raise SystemExit("integrate: --rtol / --atol and their bounds are the tolerance of an "
+                         "--expr integrand")
+    a.n = 1e9 if a.n is None else a.n
+    a.rule = a.rule or "left"
     ctx = _ctx()
     r = Integrator(a.integrand, n=int(a.n), rule=a.rule, dtype=a.dtype, div=a.div, ctx=ctx,
                    backend=a.backend).run()
     if ctx.is_root:
         print(json.dumps(r.as_dict()))
     ctx.destroy()
+    return 0
+
+
+def _integrate_adaptive(a, lo: float, hi: float) -> int:
+    """integrate --expr E --rtol R / --atol T: the integral to a tolerance (one GPU, one
+    rank). Whatever belongs to another mode is refused before anything runs."""
+    import os
+
+    from . import integrate_expr_adaptive
+
+    given = {"--n": a.n is not None, "--rule": a.rule is not None, "--ya": a.ya is not None,
+             "--yb": a.yb is not None, "--ny": a.ny is not None, "--params": bool(a.params),
+             "--linspace": bool(a.linspace)}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: --rtol / --atol choose the samples themselves: {flag} "
+                             "does not go with them")
+    if a.device == "cpu" or a.backend != "hip":
+        which = "--device cpu" if a.device == "cpu" else f"--backend {a.backend}"
+        raise SystemExit(f"integrate: --rtol / --atol have no host engine: {which} does not go "
+                         "with them")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("integrate: --rtol / --atol run as one rank: a rank environment "
+                         f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
+    opts = {k: v for k, v in (("rtol", a.rtol), ("atol", a.atol), ("panels", a.panels),
+                              ("max_depth", a.max_depth), ("max_intervals", a.max_intervals))
+            if v is not None}
+    try:
+        r = integrate_expr_adaptive(a.expr, lo, hi, **opts)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    if not r.converged:
+        print(f"integrate: not converged: err_est {r.err_est:.3g} against tol {r.tol:.3g} "
+              f"(capped {int(r.capped)}, nonfinite {r.nonfinite}, forced {r.forced})",
+              file=sys.stderr)
+    rec = r.as_dict()
+    rec["value_bits"] = "%016x" % int.from_bytes(__import__("struct").pack("<d", r.value),
+                                                 "little")
+    if a.analytic is not None:
+        rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
+    print(json.dumps(rec))
     return 0
 
 
@@ -364,6 +419,14 @@ def main(argv=None) -> int:
                     "--expr over x and y on [a, b] x [ya, yb], n x ny samples")
     ig.add_argument("--yb", type=float, default=None)
     ig.add_argument("--ny", type=float, default=None, help="samples along y (default: --n)")
+    ig.add_argument("--rtol", type=float, default=None, help="with --expr: integrate to the "
+                    "tolerance max(atol, rtol |value|), adaptively (one GPU, one rank)")
+    ig.add_argument("--atol", type=float, default=None)
+    ig.add_argument("--panels", type=int, default=None, help="--rtol / --atol: the equal "
+                    "intervals to start from (65536)")
+    ig.add_argument("--max-depth", type=int, default=None, help="bisections of one interval (60)")
+    ig.add_argument("--max-intervals", type=int, default=None, help="intervals in all (2^22)")
+    ig.set_defaults(n=None, rule=None)  # given or not: --rtol / --atol refuse them
     t2 = sub.add_parser("table2d")
     t2.add_argument("--grid", type=int, default=4096)
     t2.add_argument("--iters", type=int, default=100)

@@ -528,3 +528,67 @@ def integrate_expr_running(expr: str, a: float, b: float, n: int, rule: str = "l
         raise ValueError("integrate_expr_running backend must be 'hip' or 'cpu'")
     x = a + torch.arange(1, values.numel() + 1, dtype=torch.float64) * (every * h)
     return RunningResult(x=x.to(values.device), values=values, total=total, device_ms=ms)
+
+
+@dataclasses.dataclass
+class AdaptiveResult:
+    value: float
+    err_est: float          # the sum of the accepted intervals' |K15 - G7|
+    resabs: float           # the rule's integral of |f|
+    tol: float              # the last round's tolerance, max(atol, rtol * |value so far|)
+    converged: bool         # err_est <= tol, not capped, no non-finite interval
+    evals: int              # 15 x intervals evaluated
+    rounds: int
+    intervals: int          # the final partition
+    splits: int
+    floor: int              # accepted because |K15 - G7| is rounding noise
+    forced: int             # accepted at max_depth, or too narrow to bisect
+    nonfinite: int
+    capped: bool            # the partition would have passed max_intervals
+    device_ms: float        # the rounds (hip) or the model's run (cpu), in ms
+    expr: str
+    a: float
+    b: float
+    backend: str
+
+    def as_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+_ADAPT_FIELDS = ("value", "err_est", "resabs", "tol", "converged", "evals", "rounds",
+                 "intervals", "splits", "floor", "forced", "nonfinite", "capped")
+
+
+def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
+                            atol: float = 0.0, panels: int = 65536, max_depth: int = 60,
+                            max_intervals: int = 1 << 22,
+                            backend: str = "hip") -> AdaptiveResult:
+    """The integral of any f(x) given as one C++ expression over ``x`` on [a, b] to the
+    tolerance max(atol, rtol * |value|), with an error estimate and a ``converged`` flag:
+    adaptive Gauss-Kronrod (7, 15), the intervals bisected where the estimate misses.
+    ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr``), one GPU.
+    ``backend="cpu"``: the numpy model of the same rule (``utils.adaptive_quad``) on
+    ``expr_torch``'s evaluation of the expression (its subset of expressions); needs no GPU.
+    One rank, one f(x), a finite range."""
+    a, b = float(a), float(b)
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr(expr, a, b, rtol=rtol, atol=atol, panels=panels,
+                              max_depth=max_depth, max_intervals=max_intervals)
+        fields = {k: getattr(r, k) for k in _ADAPT_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        from .utils.adaptive_quad import adaptive_model
+
+        def f(x):
+            return expr_torch(expr, torch.from_numpy(x)).numpy()
+
+        t0 = time.perf_counter()
+        r = adaptive_model(f, a, b, rtol=rtol, atol=atol, panels=int(panels),
+                           max_depth=int(max_depth), max_intervals=int(max_intervals))
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in _ADAPT_FIELDS}
+    else:
+        raise ValueError("integrate_expr_adaptive backend must be 'hip' or 'cpu'")
+    return AdaptiveResult(**fields, device_ms=ms, expr=expr, a=a, b=b, backend=backend)

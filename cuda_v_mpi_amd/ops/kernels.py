@@ -481,6 +481,38 @@ def riemann_expr2d(expr: str, ax: float, bx: float, nx: int, ay: float, by: floa
                         getattr(m.Rule, rule), int(row_begin), int(rows))
 
 
+_EXPR_ADAPT_CACHE: dict = {}
+
+
+def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
+              panels: int = 65536, max_depth: int = 60, max_intervals: int = 1 << 22,
+              return_intervals: bool = False):
+    """The integral of any f(x) given as one C++ expression over ``x`` on [a, b] to the
+    tolerance max(atol, rtol * |value|): adaptive Gauss-Kronrod (7, 15) from ``panels`` equal
+    intervals, bisected by rounds where the estimate misses its share (at most ``max_depth``
+    times, ``max_intervals`` intervals in all), six hipRTC-compiled gfx950 kernels cached with
+    their module per (expression, device) (csrc/runtime/expr_adaptive.cpp). Returns the native
+    AdaptResult: value, err_est, resabs, tol, converged, evals, rounds, intervals, splits,
+    floor, forced, nonfinite, capped, device_ms. With ``return_intervals`` also the final
+    partition as two fp64 device tensors ``lo`` and ``hi``, running from a to b."""
+    m = native()
+    opt = m.AdaptOptions(float(rtol), float(atol), int(panels), int(max_depth),
+                         int(max_intervals))
+    m.adapt_check(float(a), float(b), opt)  # before any device call
+    dev = _device()
+    key = (expr, dev.index)
+    ea = _EXPR_ADAPT_CACHE.get(key)
+    if ea is None:
+        ea = _EXPR_ADAPT_CACHE[key] = m.ExprAdaptive(expr, dev.index)
+    if not return_intervals:
+        return ea.integrate(float(a), float(b), opt)
+    pairs = torch.empty((int(max_intervals), 2), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the rounds run on their own stream
+    r = ea.integrate(float(a), float(b), opt, pairs.data_ptr(), int(max_intervals))
+    pairs = pairs[:r.intervals]
+    return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+
+
 _EXPR_SCAN_CACHE: dict = {}
 
 

@@ -1,0 +1,135 @@
+"""The rule of the adaptive kernels (csrc/runtime/expr_adaptive.cpp, ExprAdaptive) in numpy:
+the CPU model the device is held to.
+
+Gauss-Kronrod (7, 15) on a list of intervals, bisection by rounds, the decisions of
+miint/expr.hpp in the same order, on the doubles of the rule's own table (``gk15_nodes`` and
+its weights) and at the nodes the kernels form (``gk15_abscissae``: fma(hw, t_j, c)). What the
+model does not share with the device is the order of its sums (numpy's pairwise ``sum`` here,
+butterflies and fma chains there) and the math library behind f, so a value agrees to rounding,
+not bit for bit, and a decision on the border of a bound may fall the other way.
+
+    r = adaptive_model(lambda x: 1.0 / (x * x + 1e-8), -1.0, 1.0, rtol=1e-10)
+    r["value"], r["err_est"], r["converged"], r["lo"], r["hi"]
+"""
+from __future__ import annotations
+
+import numpy as np
+
+FLOOR = 50.0 * 2.0 ** -52   # err <= FLOOR * R: the difference is rounding noise
+DEFAULTS = dict(rtol=1e-10, atol=0.0, panels=65536, max_depth=60, max_intervals=1 << 22)
+
+
+def check_options(a: float, b: float, rtol: float, atol: float, panels: int, max_depth: int,
+                  max_intervals: int) -> None:
+    """The refusals of ``adapt_check``, with the numbers named."""
+    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(b - a)):
+        raise ValueError(f"adaptive: a = {a:.17g} and b = {b:.17g} must be finite, and b - a too")
+    if not (rtol >= 0 and atol >= 0 and np.isfinite(rtol) and np.isfinite(atol)
+            and (rtol > 0 or atol > 0)):
+        raise ValueError(f"adaptive: rtol = {rtol:.17g} and atol = {atol:.17g} must be finite "
+                         "and >= 0, and not both 0")
+    if not 1 <= max_intervals <= 1 << 26:
+        raise ValueError(f"adaptive: max_intervals = {max_intervals} must be 1..2^26")
+    if not 1 <= panels <= max_intervals:
+        raise ValueError(f"adaptive: panels = {panels} must be 1..max_intervals = "
+                         f"{max_intervals}")
+    if not 0 <= max_depth <= 200:
+        raise ValueError(f"adaptive: max_depth = {max_depth} must be 0..200")
+
+
+def gk15(f, lo: np.ndarray, hi: np.ndarray):
+    """K, err = |K - G| and R of every interval [lo_i, hi_i]: the centre first, then the pairs
+    of nodes from the centre outwards, as the kernels add them."""
+    from .._native import native
+
+    m = native()
+    t, wk, wg = m.gk15_nodes(), m.gk15_weights(), m.gk7_weights()
+    x = m.gk15_abscissae(lo, hi)
+    hw = 0.5 * (hi - lo)
+    fx = np.asarray(f(x), dtype=np.float64) + np.zeros_like(x)
+    assert t[7] == 0.0 and fx.shape == x.shape
+    sk = wk[7] * fx[:, 7]
+    sg = wg[3] * fx[:, 7]
+    sa = wk[7] * np.abs(fx[:, 7])
+    for j in range(1, 8):
+        f1, f2 = fx[:, 7 - j], fx[:, 7 + j]
+        sk = sk + wk[7 + j] * (f1 + f2)
+        sa = sa + wk[7 + j] * (np.abs(f1) + np.abs(f2))
+        if j % 2 == 0:
+            sg = sg + wg[3 + j // 2] * (f1 + f2)
+    k, g = hw * sk, hw * sg
+    return k, np.abs(k - g), hw * sa
+
+
+def adaptive_model(f, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
+                   panels: int = 65536, max_depth: int = 60,
+                   max_intervals: int = 1 << 22) -> dict:
+    """The integral of f on [a, b] by the rounds of ExprAdaptive. ``f`` maps an fp64 array to
+    an fp64 array. Returns the fields of AdaptResult (``device_ms`` aside), ``peak`` (the
+    longest active list) and the final partition ``lo``, ``hi`` running from a to b."""
+    a, b = float(a), float(b)
+    check_options(a, b, rtol, atol, panels, max_depth, max_intervals)
+    out = dict(value=0.0, err_est=0.0, resabs=0.0, tol=float(atol), converged=True, evals=0,
+               rounds=0, intervals=0, splits=0, floor=0, forced=0, nonfinite=0, capped=False,
+               peak=0, lo=np.empty(0), hi=np.empty(0))
+    if a == b:
+        return out
+    swapped = a > b
+    x0, x1 = (b, a) if swapped else (a, b)
+    width = x1 - x0
+    edges = x0 + (width * np.arange(panels + 1, dtype=np.float64)) / float(panels)
+    edges[-1] = x1
+    lo, hi = edges[:-1].copy(), edges[1:].copy()
+    depth = np.zeros(panels, dtype=np.int64)
+    s_acc = e_acc = r_acc = 0.0
+    tol = float(atol)
+    done_lo, done_hi = [], []
+    with np.errstate(all="ignore"):
+        while lo.size:
+            n = lo.size
+            out["rounds"] += 1
+            out["evals"] += 15 * n
+            out["peak"] = max(out["peak"], n)
+            k, err, r = gk15(f, lo, hi)
+            t = rtol * abs(s_acc + float(k.sum()))
+            tol = float(atol) if atol > t else t          # a NaN sum: a NaN tolerance
+            w = hi - lo
+            c = lo + 0.5 * w
+            nonfinite = ~(np.isfinite(k) & np.isfinite(err))
+            within = ~nonfinite & ~(err > (tol * w) / width)
+            floor = ~nonfinite & ~within & (err <= FLOOR * r)
+            forced = (~nonfinite & ~within & ~floor
+                      & ((depth >= max_depth) | (c == lo) | (c == hi)))
+            split = ~(nonfinite | within | floor | forced)
+            n_split = int(split.sum())
+            out["nonfinite"] += int(nonfinite.sum())
+            out["floor"] += int(floor.sum())
+            out["forced"] += int(forced.sum())
+            if out["intervals"] + (n - n_split) + 2 * n_split > max_intervals:
+                out["capped"] = True   # nothing is split: the pending K and err join the totals
+                s_acc += float(k[~split].sum()) + float(k[split].sum())
+                e_acc += float(err[~split].sum()) + float(err[split].sum())
+                r_acc += float(r[~split].sum())
+                split = np.zeros(n, dtype=bool)
+                n_split = 0
+            else:
+                s_acc += float(k[~split].sum())
+                e_acc += float(err[~split].sum())
+                r_acc += float(r[~split].sum())
+            out["intervals"] += n - n_split
+            out["splits"] += n_split
+            done_lo.append(lo[~split])
+            done_hi.append(hi[~split])
+            cs = c[split]
+            lo = np.stack([lo[split], cs], axis=1).ravel()
+            hi = np.stack([cs, hi[split]], axis=1).ravel()
+            depth = np.repeat(depth[split] + 1, 2)
+    plo, phi = np.concatenate(done_lo), np.concatenate(done_hi)
+    order = np.lexsort((phi, plo))
+    plo, phi = plo[order], phi[order]
+    if swapped:
+        plo, phi = phi[::-1].copy(), plo[::-1].copy()
+    out.update(value=-s_acc if swapped else s_acc, err_est=e_acc, resabs=r_acc, tol=tol,
+               lo=plo, hi=phi)
+    out["converged"] = bool(e_acc <= tol and not out["capped"] and out["nonfinite"] == 0)
+    return out
