@@ -36,6 +36,9 @@
 // to that tolerance (ExprAdaptive: Gauss-Kronrod (7, 15), bisection where the estimate misses):
 // the value, or with --json every field of the result; a warning on stderr when not converged.
 // One GPU, one rank: no sample count, rule, sweep, curve, y range or host engine goes with it.
+// With --box A0:B0,A1:B1,... the expression is over x0, x1, ... and its integral over the box is
+// taken by a randomly shifted rank-1 lattice rule (ExprLattice): --m M for the rule of 2^M
+// points, or --rtol / --atol for the walk over M; the ranks split the points.
 //
 //   ./riemann [--n 1e9] [--gpus G] [--integrand sin|pi4|poly|train] [--rule left|mid|right]
 //             [--dtype fp64|fp32|fp32acc] [--iters K] [--block 64..1024] [--grid G] [--parity]
@@ -544,8 +547,155 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
   return 0;
 }
 
+// --expr with --box A0:B0,A1:B1,...: the integral of f(x0, ..., x{d-1}) over the box by a
+// randomly shifted rank-1 lattice rule (ExprLattice). --m M: the rule of n = 2^M points; --rtol R
+// and / or --atol T instead: the walk of M from 12 to --m-max. Ranks split the points. A number
+// that does not parse, or a flag of another mode, is refused before any device call.
+std::vector<std::string> split_commas(const std::string& text) {
+  std::vector<std::string> out(1);
+  for (char c : text) {
+    if (c == ',') out.emplace_back();
+    else out.back() += c;
+  }
+  return out;
+}
+
+LatticeBox parse_box(const std::string& text) {
+  LatticeBox box;
+  for (const std::string& side : split_commas(text)) {
+    const char* s = side.c_str();
+    char* end = nullptr;
+    const double lo = std::strtod(s, &end);
+    MIINT_CHECK(end != s && *end == ':', "--box wants A0:B0,A1:B1,... (got '" + text + "')");
+    const char* t = end + 1;
+    const double hi = std::strtod(t, &end);
+    MIINT_CHECK(end != t && *end == '\0', "--box wants A0:B0,A1:B1,... (got '" + text + "')");
+    box.emplace_back(lo, hi);
+  }
+  return box;
+}
+
+int run_expr_lattice(const cli::Args& a, int iters) {
+  for (const char* k : {"a", "b", "n", "rule", "running", "ya", "yb", "ny", "params", "linspace",
+                        "every", "running-out", "panels", "max-depth", "max-intervals"})
+    MIINT_CHECK(!a.has(k), std::string("--box integrates over a box by a lattice rule: --") + k +
+                               " does not go with it");
+  MIINT_CHECK(!cli::on_cpu(a), "--box has no host engine: --device cpu does not go with it");
+  const bool walk = a.has("rtol") || a.has("atol");
+  MIINT_CHECK(walk != a.has("m"), "--box takes --m M (the rule of 2^M points) or --rtol R / "
+                                  "--atol T (the walk over M), one of the two");
+  MIINT_CHECK(walk || !a.has("m-max"), "--m-max belongs to --box with --rtol / --atol");
+  MIINT_CHECK(!walk || !a.has("z"), "--z is the generating vector of one --m, not of a walk");
+  const LatticeBox box = parse_box(a.str("box", ""));
+  const int d = static_cast<int>(box.size());
+  LatticeOptions o;
+  o.shifts = static_cast<int>(adaptive_number(a, "shifts", o.shifts, true));
+  const double seed = adaptive_number(a, "seed", 0.0, true);
+  MIINT_CHECK(seed >= 0, "--seed must not be negative");
+  o.seed = static_cast<uint64_t>(seed);
+  o.rtol = adaptive_number(a, "rtol", 0.0, false);
+  o.atol = adaptive_number(a, "atol", 0.0, false);
+  o.m_max = static_cast<int>(adaptive_number(a, "m-max", 0.0, true));
+  MIINT_CHECK(!a.has("m-max") || o.m_max >= 1, "--m-max must be >= 1");
+  const int m = static_cast<int>(adaptive_number(a, "m", 0.0, true));
+  if (a.has("z"))
+    for (const std::string& t : split_commas(a.str("z", ""))) {
+      char* end = nullptr;
+      const unsigned long long v = std::strtoull(t.c_str(), &end, 10);
+      MIINT_CHECK(end != t.c_str() && *end == '\0' && t[0] != '-',
+                  "--z wants odd whole numbers Z0,Z1,... (got '" + a.str("z", "") + "')");
+      o.z.push_back(v);
+    }
+  const bool periodic = a.flag("periodic");
+  const bool empty = std::any_of(box.begin(), box.end(), [](const std::pair<double, double>& p) {
+    return p.first == p.second;
+  });
+  if (walk) lattice_check_walk(box, o);
+  else lattice_check(box, m, o, 0, m >= kLatticeMinM && m <= kLatticeMaxM ? 1ull << m : 0);
+  const std::string expr = a.str("expr", "");
+  // a rejected expression, or an xJ the box has no side for: before any device call
+  (void)expr_lattice_compile(expr, d, periodic);
+  const cli::Topology topo = cli::topology(a);
+  LatticeResult res;
+  double dev_ms = 0.0;
+  std::mutex mu;
+  cli::RankFacts facts;
+  cli::run_ranks(topo, [&](int rank, int dev, const Comm* comm) {
+    ExprLattice el(expr, d, periodic, dev, 0);
+    RankAgree agree(comm);
+    LatticeResult r;
+    double ms = 0.0;
+    if (walk) {
+      r = el.integrate_to(box, o, 1.0, comm);
+      ms = agree.max(r.device_ms);
+    } else {
+      uint64_t b = 0, c = 0;
+      rank_slice(1ull << m, rank, topo.world, &b, &c);
+      r = el.integrate(box, m, o, b, c, 1.0, comm);
+      r.evals = static_cast<uint64_t>(r.shifts) << m;  // the whole rule's, over all ranks
+      // barrier right before the clock starts; the slowest rank's time
+      ms = empty ? 0.0  // a side of no width: nothing was launched
+                   : agree.max(el.time(box, m, o, b, c, iters, [&] { agree.barrier(); },
+                                     [&] { fault::delay(rank); }));
+    }
+    std::lock_guard<std::mutex> g(mu);
+    if (rank == topo.rank0) {
+      res = r;
+      dev_ms = ms;
+      facts.note(comm);
+    }
+  });
+  if (topo.rank0 != 0) return 0;
+  const double secs = wall_seconds() - process_start_seconds();
+  if (walk && !res.converged)
+    std::fprintf(stderr, "riemann: not converged: err_est %.3g after %d levels (m = %d)\n",
+                 res.err_est, res.levels, res.m);
+  if (!a.flag("json")) std::printf("%.17g +- %.3g\n", res.value, res.err_est);
+  std::string bs = "[", es = "[";
+  for (size_t j = 0; j < box.size(); ++j) {
+    char b[80];
+    std::snprintf(b, sizeof b, "%s[%.17g,%.17g]", j ? "," : "", box[j].first, box[j].second);
+    bs += b;
+  }
+  for (size_t k = 0; k < res.estimates.size(); ++k) {
+    char b[40];
+    if (std::isfinite(res.estimates[k]))
+      std::snprintf(b, sizeof b, "%s%.17g", k ? "," : "", res.estimates[k]);
+    else
+      std::snprintf(b, sizeof b, "%snull", k ? "," : "");
+    es += b;
+  }
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add_raw("box", bs + "]").add("d", d)
+      .add("m", res.m).add("n", static_cast<double>(res.n)).add("shifts", res.shifts)
+      .add("seed", static_cast<double>(o.seed)).add("periodic", periodic)
+      .add("gpus", topo.world).add("value", res.value).add("err_est", res.err_est)
+      .add_raw("estimates", es + "]").add("evals", static_cast<double>(res.evals))
+      .add("levels", res.levels).add("converged", res.converged);
+  if (walk) rec.add("rtol", o.rtol).add("atol", o.atol);
+  char bits[24];
+  uint64_t w = 0;
+  std::memcpy(&w, &res.value, sizeof w);
+  std::snprintf(bits, sizeof bits, "%016llx", static_cast<unsigned long long>(w));
+  rec.add("value_bits", bits);
+  std::memcpy(&w, &res.err_est, sizeof w);
+  std::snprintf(bits, sizeof bits, "%016llx", static_cast<unsigned long long>(w));
+  rec.add("err_est_bits", bits);
+  facts.add(rec, topo);
+  if (a.has("analytic")) {
+    const double exact = a.num("analytic", 0.0);
+    rec.add("analytic", exact).add("abs_err", std::fabs(res.value - exact));
+  }
+  cli::emit(a, rec.add("device_ms", dev_ms)
+                   .add("samples_per_s",
+                        dev_ms > 0 ? static_cast<double>(res.evals) / (dev_ms * 1e-3) : 0.0)
+                   .add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (a.has("box")) return run_expr_lattice(a, iters);
   if (adaptive_requested(a)) return run_expr_adaptive(a, cfg);
   if (a.has("ya")) return run_expr2d(a, cfg, nd, iters);
   if (a.flag("running")) return run_expr_running(a, cfg, nd);
@@ -610,6 +760,8 @@ constexpr const char* kUsage =
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
     "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
     "                [--max-intervals M]]\n"
+    "               [--expr EXPR --box A0:B0,A1:B1,... --m M | --rtol R [--atol T] [--m-max M]\n"
+    "                [--shifts R] [--seed S] [--periodic] [--z Z0,Z1,...] [--analytic V]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
     "two lines, or one JSON record with --json. Multi-GPU: --gpus G, torchrun or miintrun.\n"
     "--running: the running integral F(x) = h * sum of f up to x at every sample (one GPU,\n"
@@ -626,7 +778,16 @@ constexpr const char* kUsage =
     "  prints the value, and a warning on stderr when not converged; --json: value, err_est,\n"
     "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
     "  device_ms. One GPU, one rank, no host engine: refused with --n, --rule, --running, --ya,\n"
-    "  --params, --linspace, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n";
+    "  --params, --linspace, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n"
+    "--box A0:B0,A1:B1,...: the integral of --expr over x0, x1, ... (at most 16 sides) by a randomly\n"
+    "  shifted rank-1 lattice rule: --m M for n = 2^M points (built-in generating vectors for M =\n"
+    "  10..26, else --z Z0,Z1,... odd and below n), --shifts R random shifts (default 16) from\n"
+    "  --seed S, the tent transform unless --periodic; or --rtol R / --atol T (here the lattice's\n"
+    "  tolerance): M walks from 12 to --m-max until err_est <= max(T, R |value|). Prints 'value +-\n"
+    "  err_est' (one standard error over the shifts); --json: value, err_est, estimates, m, n,\n"
+    "  shifts, evals, levels, converged, device_ms. Ranks split the points (--gpus, --loopback,\n"
+    "  rank environment). Refused with --a, --b, --n, --rule, --running, --ya, --params,\n"
+    "  --linspace, --panels, --max-depth, --max-intervals or --device cpu.\n";
 
 int main(int argc, char** argv) {
   try {
@@ -685,6 +846,12 @@ int main(int argc, char** argv) {
     MIINT_CHECK(adaptive_requested(a) ||
                     !(a.has("panels") || a.has("max-depth") || a.has("max-intervals")),
                 "--panels / --max-depth / --max-intervals belong to --rtol / --atol");
+    MIINT_CHECK(a.has("expr") || !a.has("box"),
+                "--box is the box of an --expr integrand over x0, x1, ...");
+    for (const char* k : {"m", "shifts", "seed", "z", "periodic", "m-max"})
+      MIINT_CHECK(a.has("box") || !a.has(k),
+                  std::string("--") + k + " belongs to --box (the lattice rule of an --expr "
+                  "integrand)");
     if (a.has("expr")) return run_expr(a, cfg, nd, iters);
     if (cli::on_cpu(a)) return run_host(a, cfg, nd, iters);
     const cli::Topology topo = cli::topology(a);

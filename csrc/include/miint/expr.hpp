@@ -29,6 +29,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "miint/comm.hpp"
@@ -474,6 +475,163 @@ class ExprAdaptive {
   DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 4 counters; the split prefix
   DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive.cpp)
   PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
+  Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+};
+
+// ---------------------------------------------------------------------------------------
+// Integrals over a box in up to 16 variables: f(x0, ..., x{d-1}) on [a_0, b_0] x ... by a
+// randomly shifted rank-1 lattice rule, with an error estimate from the shifts.
+//
+// The tensor route ends at two variables (ExprIntegrator2D needs 2^30 samples for a 32768^2
+// rule). Here n = 2^m points serve any d <= 16. With a generating vector z (d odd entries below
+// n), point i of shift r has in dimension j the 32-bit fixed-point fraction
+//   u = (((i z_j) mod n) << (32 - m)) + shift[r][j]   (mod 2^32)
+// and, by default, the tent transform of it, which makes a smooth non-periodic integrand
+// converge like a periodic one:
+//   s = (int32)u >> 31, w = (u ^ s) & 0x7FFFFFFF, t = fma((double)w, 2^-31, 2^-32)
+// exactly 1 - |2 tau - 1| of the centred fraction tau = (u + 1/2) / 2^32. `periodic` skips the
+// tent: t = fma((double)u, 2^-32, 2^-33). Either way t lies strictly inside (0, 1), so no face
+// of the box is evaluated, and x_j = fma(t, b_j - a_j, a_j) with b_j - a_j rounded once on the
+// host. Every t is a dyadic rational, so piecewise-linear and indicator integrands on boxes of
+// power-of-two widths sum exactly in fp64. shift[r][j] is the high 32 bits of splitmix64 at
+// the counter r * 16 + j (lattice_shifts), or the caller's own R x d words.
+//   est_r = (vol * scale) * S_r / n, S_r the sum of f over the n points of shift r
+//   value = (sum est_r) / R in index order
+//   err_est = sqrt(sum (est_r - value)^2 / (R (R - 1))): one standard error, not a bound;
+//             +inf for R = 1
+// Three kernels (expr_lattice.cpp), compiled per (expression, d, periodic):
+//
+//   miint_lattice_partials  grid (gx, gy): gx point slices x gy shift lanes. A lane walks a
+//                           contiguous run of point indices (the prelude's balanced split). At
+//                           its first point it forms each u_j from the 64-bit product i0 z_j;
+//                           after that a sample costs per dimension one wrapping 32-bit add of
+//                           the uniform step z_j << (32 - m) (the wrap is the mod n), the tent's
+//                           shift, xor and and, one conversion and two fma; then f and one add
+//                           into one of four accumulators. One partial per (shift, bx)
+//   miint_lattice_close     per shift, the closing step over its gx partials -> S_r
+//   (world > 1)             all-reduce of the R sums
+//   miint_lattice_finish    one workgroup: est_r, value, err_est in the order above, stored to
+//                           pinned host memory
+//
+// gx depends on the slice's point count (and an explicit grid) only, never on R, so shift r's
+// estimate is bitwise the same alone, among 17 shifts and at any position. No workgroup waits
+// on another and every sum has a fixed order: bitwise reproducible. a_j > b_j negates the
+// volume; a_j == b_j gives 0 with no launch.
+//
+// Generating vectors are of Korobov form, z_j = a^j mod n, one built-in a for each m of
+// kLatticeBuiltinMin..kLatticeBuiltinMax, chosen by tools/lattice_search.py; for another m, or
+// on request, the caller passes z. integrate_to walks m upwards, each level a fresh rule with
+// the same shifts, to the first level with err_est <= max(atol, rtol |value|).
+// ---------------------------------------------------------------------------------------
+constexpr int kLatticeMaxDim = 16;
+constexpr int kLatticeMinM = 2, kLatticeMaxM = 30;
+constexpr int kLatticeMaxShifts = 4096;
+constexpr int kLatticeBuiltinMin = 10, kLatticeBuiltinMax = 26;
+constexpr int kLatticeMaxGrid = 2048;  // gx, and about gx * gy
+// Least points per lane worth one more workgroup along the points (ExprSweep's measured 256).
+constexpr uint64_t kLatticeMinPointsPerLane = 256;
+
+// The sides of the box: (a_j, b_j) for j < d.
+using LatticeBox = std::vector<std::pair<double, double>>;
+
+struct LatticeOptions {
+  int shifts = 16;                    // R, when shift_words is empty
+  uint64_t seed = 0;                  // of lattice_shifts
+  std::vector<uint32_t> shift_words;  // R x d explicit shift words, row-major (R from the size)
+  std::vector<uint64_t> z;            // d entries; empty: the built-in vector of m
+  double rtol = 0.0, atol = 0.0;      // integrate_to only
+  int m_min = 12;                     // integrate_to: the first level
+  int m_max = 0;                      // integrate_to: the last one; 0 or above the built-in
+                                      // range: kLatticeBuiltinMax
+};
+struct LatticeResult {
+  double value = 0.0, err_est = 0.0;
+  std::vector<double> estimates;  // est_r
+  int m = 0;                      // the (last) level
+  uint64_t n = 0;                 // 2^m
+  int shifts = 0;                 // R
+  uint64_t evals = 0;  // integrate: R x count of this call's slice; integrate_to: R x n, all levels
+  int levels = 1;
+  bool converged = false;  // integrate_to: the tolerance was met; integrate asks none: false
+  double device_ms = 0.0;  // events around the call's kernels (and collectives)
+};
+
+// The built-in Korobov vector z_j = a^j mod 2^m, j < d. Throws, naming m, outside the table.
+std::vector<uint64_t> lattice_generator(int m, int d);
+// The table's multiplier a of m (tools/lattice_search.py prints it).
+uint64_t lattice_multiplier(int m);
+// shift[r][j], row-major R x d: the high 32 bits of splitmix64 at counter q = r * 16 + j:
+// z = seed + (q + 1) 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+// z = (z ^ z >> 27) 0x94D049BB133111EB; z ^= z >> 31.
+std::vector<uint32_t> lattice_shifts(uint64_t seed, int shifts, int d);
+// Throws, naming the numbers, unless 1 <= d <= 16, 2 <= m <= 30, the box and the scale are
+// finite (the widths too), 1 <= R <= 4096 (shift_words a multiple of d), every given z_j is
+// odd and below n (or m has a built-in vector) and [begin, begin + count) lies in [0, n). No
+// device needed; nothing is launched after a refusal.
+void lattice_check(const LatticeBox& box, int m, const LatticeOptions& opt, uint64_t begin,
+                   uint64_t count, double scale = 1.0);
+// The same for integrate_to: rtol and atol finite, >= 0 and not both 0, m_min <= the clamped
+// m_max, both in the built-in range, no explicit z.
+void lattice_check_walk(const LatticeBox& box, const LatticeOptions& opt, double scale = 1.0);
+struct LatticeShape {
+  int gx = 1, gy = 1;
+};
+// Launch shape for `count` points and R shifts (no device needed): gx = grid if given, else
+// clamp(ceil(count / (256 * kLatticeMinPointsPerLane)), 1, 2048); gy = clamp(2048 / gx, 1, R).
+LatticeShape lattice_shape(uint64_t count, int shifts, int grid = 0);
+// Kernel source for f(x0..x{d-1}); an xJ at or above d fails in the compiler.
+std::string expr_lattice_source(const std::string& expr, int d, bool periodic = false);
+// hipRTC compile for gfx950 (no device needed), cached per (expression, d, periodic).
+std::string expr_lattice_compile(const std::string& expr, int d, bool periodic = false);
+
+class ExprLattice {
+ public:
+  ExprLattice(const std::string& expr, int d, bool periodic = false, int device = 0,
+              int grid = 0);
+  ExprLattice(const ExprLattice&) = delete;
+  ExprLattice& operator=(const ExprLattice&) = delete;
+  // The rule of level m on points [begin, begin + count) of its n = 2^m. With a communicator
+  // of more than one rank the ranks' sums S_r are all-reduced between close and finish, so
+  // every rank gets the whole rule's result. Synchronous.
+  LatticeResult integrate(const LatticeBox& box, int m, const LatticeOptions& opt = {},
+                          uint64_t begin = 0, uint64_t count = ~0ull, double scale = 1.0,
+                          const Comm* comm = nullptr);
+  // The walk over m described above; with a communicator every level's points are split by
+  // rank_slice over its ranks. result.levels and result.evals count every level, the other
+  // fields are the last level's.
+  LatticeResult integrate_to(const LatticeBox& box, const LatticeOptions& opt, double scale = 1.0,
+                             const Comm* comm = nullptr);
+  // Device ms per integrate() of one rank over `iters` back-to-back ones (shifts uploaded once,
+  // before the clock). Hooks as in ExprIntegrator::time.
+  double time(const LatticeBox& box, int m, const LatticeOptions& opt, uint64_t begin,
+              uint64_t count, int iters, const std::function<void()>& at_start = {},
+              const std::function<void()>& at_end = {});
+  // Partials go to the caller's device memory (`capacity` doubles) instead of the object's
+  // own buffer; a call whose R x gx partials would not fit is refused up front. nullptr: back
+  // to the object's buffer.
+  void use_partials(double* device_ptr, uint64_t capacity);
+  const std::string& expression() const { return expr_; }
+  int dim() const { return d_; }
+  bool periodic() const { return periodic_; }
+
+ private:
+  struct Plan;
+  Plan plan(const LatticeBox& box, int m, const LatticeOptions& opt, uint64_t begin,
+            uint64_t count, double scale) const;
+  void upload(const Plan& p, hipStream_t s);
+  void enqueue(const Plan& p, const Comm* comm, hipStream_t s);
+  std::string expr_;
+  int d_;
+  bool periodic_;
+  int device_, grid_;
+  Stream stream_;
+  DeviceBuffer<unsigned> shifts_;
+  DeviceBuffer<double> partials_, sums_;
+  double* user_partials_ = nullptr;
+  uint64_t user_capacity_ = 0;
+  PinnedBuffer<unsigned> host_shifts_;
+  PinnedBuffer<double> host_out_;  // [0] value, [1] err_est, [2 + r] est_r
   Event e0_, e1_;
   detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };

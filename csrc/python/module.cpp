@@ -1095,6 +1095,138 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprAdaptive::expression);
 
+  // integrals over a box in up to 16 variables: randomly shifted rank-1 lattice rules
+  m.attr("LATTICE_MAX_DIM") = kLatticeMaxDim;
+  m.attr("LATTICE_MIN_M") = kLatticeMinM;
+  m.attr("LATTICE_MAX_M") = kLatticeMaxM;
+  m.attr("LATTICE_MAX_SHIFTS") = kLatticeMaxShifts;
+  m.attr("LATTICE_BUILTIN_M_MIN") = kLatticeBuiltinMin;
+  m.attr("LATTICE_BUILTIN_M_MAX") = kLatticeBuiltinMax;
+  m.def("lattice_generator", &lattice_generator, py::arg("m"), py::arg("d"),
+        "the built-in Korobov vector z_j = a^j mod 2^m, j < d");
+  m.def("lattice_multiplier", &lattice_multiplier, py::arg("m"),
+        "the built-in table's Korobov multiplier a of m");
+  m.def("lattice_shifts",
+        [](uint64_t seed, int shifts, int d) {
+          const std::vector<uint32_t> w = lattice_shifts(seed, shifts, d);
+          py::array_t<uint32_t> a({static_cast<py::ssize_t>(shifts), static_cast<py::ssize_t>(d)});
+          std::copy(w.begin(), w.end(), a.mutable_data());
+          return a;
+        },
+        py::arg("seed"), py::arg("shifts"), py::arg("d"),
+        "the shifts x d shift words of a seed: the high 32 bits of splitmix64 at r * 16 + j");
+  py::class_<LatticeOptions>(m, "LatticeOptions", "shifts, generating vector and tolerances")
+      .def(py::init([](int shifts, uint64_t seed, std::vector<uint32_t> shift_words,
+                       std::vector<uint64_t> z, double rtol, double atol, int m_min, int m_max) {
+             LatticeOptions o;
+             o.shifts = shifts;
+             o.seed = seed;
+             o.shift_words = std::move(shift_words);
+             o.z = std::move(z);
+             o.rtol = rtol;
+             o.atol = atol;
+             o.m_min = m_min;
+             o.m_max = m_max;
+             return o;
+           }),
+           py::arg("shifts") = 16, py::arg("seed") = 0,
+           py::arg("shift_words") = std::vector<uint32_t>(),
+           py::arg("z") = std::vector<uint64_t>(), py::arg("rtol") = 0.0, py::arg("atol") = 0.0,
+           py::arg("m_min") = 12, py::arg("m_max") = 0)
+      .def_readwrite("shifts", &LatticeOptions::shifts)
+      .def_readwrite("seed", &LatticeOptions::seed)
+      .def_readwrite("shift_words", &LatticeOptions::shift_words)
+      .def_readwrite("z", &LatticeOptions::z)
+      .def_readwrite("rtol", &LatticeOptions::rtol)
+      .def_readwrite("atol", &LatticeOptions::atol)
+      .def_readwrite("m_min", &LatticeOptions::m_min)
+      .def_readwrite("m_max", &LatticeOptions::m_max);
+  py::class_<LatticeResult>(m, "LatticeResult", "value, error estimate and estimates of one call")
+      .def_readonly("value", &LatticeResult::value)
+      .def_readonly("err_est", &LatticeResult::err_est)
+      .def_property_readonly("estimates",
+                             [](const LatticeResult& r) {
+                               return py::array_t<double>(
+                                   static_cast<py::ssize_t>(r.estimates.size()),
+                                   r.estimates.data());
+                             })
+      .def_readonly("m", &LatticeResult::m)
+      .def_readonly("n", &LatticeResult::n)
+      .def_readonly("shifts", &LatticeResult::shifts)
+      .def_readonly("evals", &LatticeResult::evals)
+      .def_readonly("levels", &LatticeResult::levels)
+      .def_readonly("converged", &LatticeResult::converged)
+      .def_readonly("device_ms", &LatticeResult::device_ms)
+      .def("as_dict", [](const LatticeResult& r) {
+        py::dict d;
+        d["value"] = r.value;
+        d["err_est"] = r.err_est;
+        d["estimates"] = r.estimates;
+        d["m"] = r.m;
+        d["n"] = r.n;
+        d["shifts"] = r.shifts;
+        d["evals"] = r.evals;
+        d["levels"] = r.levels;
+        d["converged"] = r.converged;
+        d["device_ms"] = r.device_ms;
+        return d;
+      });
+  m.def("lattice_check", &lattice_check, py::arg("box"), py::arg("m"), py::arg("options"),
+        py::arg("begin"), py::arg("count"), py::arg("scale") = 1.0,
+        "raise, naming the numbers, unless ExprLattice.integrate takes the box, the level, the "
+        "options and the slice");
+  m.def("lattice_check_walk", &lattice_check_walk, py::arg("box"), py::arg("options"),
+        py::arg("scale") = 1.0,
+        "raise, naming the numbers, unless ExprLattice.integrate_to takes the box and the options");
+  m.def("lattice_shape", [](uint64_t count, int shifts, int grid) {
+          const LatticeShape s = lattice_shape(count, shifts, grid);
+          return py::make_tuple(s.gx, s.gy);
+        },
+        py::arg("count"), py::arg("shifts"), py::arg("grid") = 0,
+        "(gx, gy) of a lattice launch; gx never depends on shifts");
+  m.def("expr_lattice_source", &expr_lattice_source, py::arg("expr"), py::arg("d"),
+        py::arg("periodic") = false,
+        "source of the lattice kernels generated for an expression over x0..x{d-1}");
+  m.def("expr_lattice_compile", compiled(&expr_lattice_compile), py::arg("expr"), py::arg("d"),
+        py::arg("periodic") = false,
+        "compile the lattice kernels for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprLattice>(m, "ExprLattice",
+                          "the integral of f(x0..x{d-1}) over a box by a randomly shifted rank-1 "
+                          "lattice rule (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int, bool, int, int>(), py::arg("expr"), py::arg("d"),
+           py::arg("periodic") = false, py::arg("device") = 0, py::arg("grid") = 0)
+      .def("integrate",
+           [](ExprLattice& e, const LatticeBox& box, int lm, const LatticeOptions& o,
+              uint64_t begin, py::object count, double scale, const Comm* comm) {
+             const uint64_t c = count.is_none() ? ~0ull : count.cast<uint64_t>();
+             py::gil_scoped_release nogil;
+             return e.integrate(box, lm, o, begin, c, scale, comm);
+           },
+           py::arg("box"), py::arg("m"), py::arg("options") = LatticeOptions(),
+           py::arg("begin") = 0, py::arg("count") = py::none(), py::arg("scale") = 1.0,
+           py::arg("comm") = nullptr)
+      .def("integrate_to", &ExprLattice::integrate_to, py::arg("box"), py::arg("options"),
+           py::arg("scale") = 1.0, py::arg("comm") = nullptr,
+           py::call_guard<py::gil_scoped_release>())
+      .def("time",
+           [](ExprLattice& e, const LatticeBox& box, int lm, const LatticeOptions& o,
+              uint64_t begin, py::object count, int iters) {
+             const uint64_t c = count.is_none() ? ~0ull : count.cast<uint64_t>();
+             py::gil_scoped_release nogil;
+             return e.time(box, lm, o, begin, c, iters);
+           },
+           py::arg("box"), py::arg("m"), py::arg("options") = LatticeOptions(),
+           py::arg("begin") = 0, py::arg("count") = py::none(), py::arg("iters") = 10)
+      .def("use_partials",
+           [](ExprLattice& e, uintptr_t ptr, uint64_t capacity) {
+             e.use_partials(reinterpret_cast<double*>(ptr), capacity);
+           },
+           py::arg("device_ptr"), py::arg("capacity"),
+           "partials go to the caller's device memory (capacity doubles); 0: the object's own")
+      .def_property_readonly("expression", &ExprLattice::expression)
+      .def_property_readonly("dim", &ExprLattice::dim)
+      .def_property_readonly("periodic", &ExprLattice::periodic);
+
   // ------------------------------------------------------------------ host (CPU) engine
   m.def("host_isa", &host_isa, "vector ISA the host kernels dispatch to: avx512|avx2|base");
   py::class_<HostPool>(m, "HostPool", "persistent host worker threads (0 = one per core)")

@@ -9,6 +9,7 @@ SURVEY §2.6) on top of the Python API, and adds JSON output:
     integrate   any integrand, JSON result                        [--integrand --n --rule ...]
                 or any f(x):  --expr "exp(-x*x)" --a 0 --b 3 (compiled at run time, hipRTC)
                 or to a tolerance: --expr "1.0/sqrt(x)" --a 0 --b 1 --rtol 1e-10
+                or over a box: --expr "exp(-(x0*x0+x1*x1+x2*x2))" --box 0:1,0:1,0:3 --m 20
     table2d     2-D velocity field v(x) v(y), bilinear, JSON      [--grid 4096 --iters 100]
     oracle      print every SURVEY §6.1 oracle value (CPU only)
     scale       GPU-count sweep 1,2,4,8: weak/strong efficiency, RCCL latency [--gpus 1,2,4,8]
@@ -190,6 +191,9 @@ def cmd_integrate(a) -> int:
     if a.expr:  # any f(x): compiled at run time with hipRTC (ops.kernels.riemann_expr)
         from .ops import kernels
 
+        if a.box:
+            return _integrate_lattice(a)
+        _no_lattice_flags(a)
         lo = 0.0 if a.a is None else a.a
         hi = 1.0 if a.b is None else a.b
         if a.rtol is not None or a.atol is not None:
@@ -249,6 +253,9 @@ def cmd_integrate(a) -> int:
         print(json.dumps(rec))
         return 0
 
+    if a.box:
+        raise SystemExit("integrate: --box is the box of an --expr integrand over x0, x1, ...")
+    _no_lattice_flags(a)
     if (a.rtol is not None or a.atol is not None or a.panels is not None
             or a.max_depth is not None or a.max_intervals is not None):
         raise SystemExit("integrate: --rtol / --atol and their bounds are the tolerance of an "
@@ -261,6 +268,68 @@ def cmd_integrate(a) -> int:
     if ctx.is_root:
         print(json.dumps(r.as_dict()))
     ctx.destroy()
+    return 0
+
+
+def _no_lattice_flags(a) -> None:
+    for flag, on in (("--m", a.m is not None), ("--shifts", a.shifts is not None),
+                     ("--seed", a.seed is not None), ("--z", bool(a.z)),
+                     ("--periodic", a.periodic), ("--m-max", a.m_max is not None)):
+        if on:
+            raise SystemExit(f"integrate: {flag} belongs to --box (the lattice rule of an "
+                             "--expr integrand)")
+
+
+def _integrate_lattice(a) -> int:
+    """integrate --expr E --box A0:B0,A1:B1,... --m M | --rtol R [--atol T]: the integral over a
+    box by a randomly shifted lattice rule (one GPU, or --backend cpu for the numpy model).
+    Whatever belongs to another mode is refused before anything runs."""
+    from . import integrate_expr_nd
+
+    given = {"--a": a.a is not None, "--b": a.b is not None, "--n": a.n is not None,
+             "--rule": a.rule is not None, "--ya": a.ya is not None, "--yb": a.yb is not None,
+             "--ny": a.ny is not None, "--params": bool(a.params),
+             "--linspace": bool(a.linspace), "--panels": a.panels is not None,
+             "--max-depth": a.max_depth is not None,
+             "--max-intervals": a.max_intervals is not None}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: --box integrates over a box by a lattice rule: {flag} "
+                             "does not go with it")
+    if a.device == "cpu" or a.backend == "host":
+        which = "--device cpu" if a.device == "cpu" else "--backend host"
+        raise SystemExit(f"integrate: --box has no host engine: {which} does not go with it")
+    walk = a.rtol is not None or a.atol is not None
+    if walk == (a.m is not None):
+        raise SystemExit("integrate: --box takes --m M (the rule of 2^M points) or --rtol R / "
+                         "--atol T (the walk over M), one of the two")
+    if a.m_max is not None and not walk:
+        raise SystemExit("integrate: --m-max belongs to --box with --rtol / --atol")
+    try:
+        box = [tuple(float(v) for v in side.split(":")) for side in a.box.split(",")]
+        if any(len(side) != 2 for side in box):
+            raise ValueError
+        z = [int(v) for v in a.z.split(",")] if a.z else None
+    except ValueError:
+        raise SystemExit(f"integrate: --box wants A0:B0,A1:B1,... and --z Z0,Z1,... (got "
+                         f"{a.box!r}, {a.z!r})") from None
+    try:
+        r = integrate_expr_nd(a.expr, box, m=a.m, rtol=a.rtol if walk else None,
+                              atol=(a.atol or 0.0) if walk else 0.0,
+                              shifts=16 if a.shifts is None else a.shifts, seed=a.seed or 0,
+                              periodic=a.periodic, z=z, backend=a.backend, m_max=a.m_max)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    if walk and not r.converged:
+        print(f"integrate: not converged: err_est {r.err_est:.3g} after {r.levels} levels "
+              f"(m = {r.m})", file=sys.stderr)
+    rec = r.as_dict()
+    pack = __import__("struct").pack
+    rec["value_bits"] = "%016x" % int.from_bytes(pack("<d", r.value), "little")
+    rec["err_est_bits"] = "%016x" % int.from_bytes(pack("<d", r.err_est), "little")
+    if a.analytic is not None:
+        rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
+    print(json.dumps(rec))
     return 0
 
 
@@ -426,6 +495,15 @@ def main(argv=None) -> int:
                     "intervals to start from (65536)")
     ig.add_argument("--max-depth", type=int, default=None, help="bisections of one interval (60)")
     ig.add_argument("--max-intervals", type=int, default=None, help="intervals in all (2^22)")
+    ig.add_argument("--box", default="", help="with --expr over x0, x1, ...: A0:B0,A1:B1,..., the "
+                    "integral over the box by a randomly shifted lattice rule (--m M, or --rtol / "
+                    "--atol for the walk over M)")
+    ig.add_argument("--m", type=int, default=None, help="--box: n = 2^M points per shift")
+    ig.add_argument("--shifts", type=int, default=None, help="--box: random shifts (16)")
+    ig.add_argument("--seed", type=int, default=None, help="--box: the shifts' seed (0)")
+    ig.add_argument("--z", default="", help="--box --m: the generating vector Z0,Z1,...")
+    ig.add_argument("--periodic", action="store_true", help="--box: no tent transform")
+    ig.add_argument("--m-max", type=int, default=None, help="--box --rtol: the last level")
     ig.set_defaults(n=None, rule=None)  # given or not: --rtol / --atol refuse them
     t2 = sub.add_parser("table2d")
     t2.add_argument("--grid", type=int, default=4096)

@@ -24,6 +24,7 @@ import dataclasses
 import math
 import time
 
+import numpy as np
 import torch
 
 from .models import integrands
@@ -448,14 +449,16 @@ _TORCH_MATH = {
 }
 
 
-def expr_torch(expr: str, x: torch.Tensor, y: torch.Tensor | None = None) -> torch.Tensor:
+def expr_torch(expr: str, x: torch.Tensor, y: torch.Tensor | None = None,
+               names: dict | None = None) -> torch.Tensor:
     """The torch form of a run-time expression: f(x) element-wise in x's dtype, for an
     expression made of numbers, ``x``, + - * /, parentheses and the math functions torch has
     (sin, exp, pow, fabs, ...). The syntax tree is walked, nothing is ``eval``-ed; anything
     else (``?:``, comparisons, other names) raises ValueError: the cpu backend covers the
     arithmetic subset of what the hipRTC backends compile. With ``y`` given the name ``y``
     resolves to it and the result has the broadcast shape of x and y (f(x, y)); without it
-    ``y`` is an unknown name, as before."""
+    ``y`` is an unknown name, as before. ``names`` maps further names to tensors (``x0`` ...
+    ``x15`` of ``integrate_expr_nd``); they are looked up before ``x`` and ``y``."""
     import ast
 
     try:
@@ -472,6 +475,8 @@ def expr_torch(expr: str, x: torch.Tensor, y: torch.Tensor | None = None) -> tor
             return walk(node.body)
         if isinstance(node, ast.Constant) and type(node.value) in (int, float):
             return const(node.value)
+        if isinstance(node, ast.Name) and names is not None and node.id in names:
+            return names[node.id]
         if isinstance(node, ast.Name) and node.id == "x":
             return x
         if isinstance(node, ast.Name) and node.id == "y" and y is not None:
@@ -592,3 +597,83 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
     else:
         raise ValueError("integrate_expr_adaptive backend must be 'hip' or 'cpu'")
     return AdaptiveResult(**fields, device_ms=ms, expr=expr, a=a, b=b, backend=backend)
+
+
+@dataclasses.dataclass
+class LatticeResult:
+    value: float
+    err_est: float          # one standard error over the shifts, not a bound; inf for one shift
+    estimates: list         # est_r, one per shift
+    m: int                  # the (last) level: n = 2^m points per shift
+    n: int
+    shifts: int
+    evals: int              # shifts x points, every level counted
+    levels: int
+    converged: bool         # a tolerance was asked and met
+    device_ms: float        # the kernels (hip) or the model's run (cpu), in ms
+    expr: str
+    box: list
+    periodic: bool
+    backend: str
+
+    def as_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+def integrate_expr_nd(expr: str, box, m: int | None = None, rtol: float | None = None,
+                      atol: float = 0.0, shifts: int = 16, seed: int = 0, periodic: bool = False,
+                      z=None, backend: str = "hip", m_min: int = 12,
+                      m_max: int | None = None) -> LatticeResult:
+    """The integral of any f(x0, ..., x{d-1}) given as one C++ expression over a box
+    ``[(a0, b0), ...]`` of 1 <= d <= 16 sides, by a randomly shifted rank-1 lattice rule with
+    n = 2^m points and ``shifts`` random shifts: the value, ``err_est`` (one standard error over
+    the shifts) and the shifts' estimates. With ``m`` the rule of that level (``z``: its
+    generating vector; default: the built-in Korobov vector of m = 10..26). With ``rtol`` and /
+    or ``atol`` instead, m walks from ``m_min`` to ``m_max`` and stops at the first level whose
+    err_est <= max(atol, rtol * |value|); ``converged`` says whether one did. The tent transform
+    is applied unless ``periodic``. ``backend="hip"``: the hipRTC-compiled gfx950 kernels
+    (``ops.kernels.lattice_expr``), one GPU. ``backend="cpu"``: the numpy model of the same rule
+    (``utils.lattice_rule``) on ``expr_torch``'s evaluation of the expression (its arithmetic
+    subset); needs no GPU."""
+    box = [(float(lo), float(hi)) for lo, hi in box]
+    walk = rtol is not None or (atol is not None and atol > 0.0)
+    if (m is None) != walk:
+        raise ValueError("integrate_expr_nd takes a level m, or a tolerance (rtol and / or atol) "
+                         "to walk m to, not both and not neither")
+    if backend == "hip":
+        from .ops import kernels
+
+        r, _ = kernels.lattice_expr(expr, box, m=m, rtol=rtol, atol=atol, shifts=shifts,
+                                    seed=seed, periodic=periodic, z=z, m_min=m_min, m_max=m_max)
+        fields = dict(value=r.value, err_est=r.err_est, estimates=r.estimates.tolist(), m=r.m,
+                      n=r.n, shifts=r.shifts, evals=r.evals, levels=r.levels,
+                      converged=r.converged)
+        ms = r.device_ms
+    elif backend == "cpu":
+        from .utils import lattice_rule
+
+        def f(x):
+            cols = {f"x{j}": torch.from_numpy(np.ascontiguousarray(x[:, j]))
+                    for j in range(x.shape[1])}
+            return expr_torch(expr, cols["x0"], names=cols).numpy()
+
+        t0 = time.perf_counter()
+        if walk:
+            if z is not None:
+                raise ValueError("lattice: a walk over m takes the built-in vectors (z belongs "
+                                 "to one m)")
+            r = lattice_rule.lattice_to_tolerance(f, box, rtol=rtol or 0.0, atol=atol or 0.0,
+                                                  m_min=m_min, m_max=m_max, shifts=shifts,
+                                                  seed=seed, periodic=periodic)
+        else:
+            r = lattice_rule.lattice_model(f, box, int(m), shifts=shifts, seed=seed,
+                                           periodic=periodic, z=z)
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = dict(value=r["value"], err_est=r["err_est"],
+                      estimates=r["estimates"].tolist(), m=r["m"], n=r["n"],
+                      shifts=int(r["shifts"].shape[0]), evals=int(r["evals"]),
+                      levels=r["levels"], converged=r["converged"])
+    else:
+        raise ValueError("integrate_expr_nd backend must be 'hip' or 'cpu'")
+    return LatticeResult(**fields, device_ms=ms, expr=expr, box=box, periodic=bool(periodic),
+                         backend=backend)

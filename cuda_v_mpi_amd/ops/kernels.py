@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from .._native import native
@@ -511,6 +512,52 @@ def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 
     r = ea.integrate(float(a), float(b), opt, pairs.data_ptr(), int(max_intervals))
     pairs = pairs[:r.intervals]
     return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+
+
+_EXPR_LATTICE_CACHE: dict = {}
+
+
+def lattice_expr(expr: str, box, m: int | None = None, rtol: float | None = None,
+                 atol: float = 0.0, shifts: int = 16, seed: int = 0, periodic: bool = False,
+                 z=None, shift_words=None, begin: int = 0, count: int | None = None,
+                 scale: float = 1.0, grid: int = 0, m_min: int = 12, m_max: int | None = None,
+                 comm=None):
+    """The integral of any f(x0, ..., x{d-1}) given as one C++ expression over the box
+    ``[(a0, b0), ...]`` (d <= 16 sides) by a randomly shifted rank-1 lattice rule: n = 2^m
+    points, ``shifts`` random shifts (or the explicit ``shift_words``, R x d uint32), the tent
+    transform unless ``periodic``; three hipRTC-compiled gfx950 kernels cached with their module
+    per (expression, d, periodic, device, grid) (csrc/runtime/expr_lattice.cpp). With ``m`` the
+    rule of that level on points [begin, begin + count) (default: all), the ranks of ``comm``
+    all-reducing their sums; with ``rtol`` / ``atol`` instead the walk of m from ``m_min`` to
+    ``m_max``. Returns the native LatticeResult (value, err_est, estimates, m, n, shifts, evals,
+    levels, converged, device_ms) and the estimates as an fp64 tensor on the host (the finish
+    kernel stores them to pinned memory)."""
+    mod = native()
+    box = [(float(lo), float(hi)) for lo, hi in box]
+    d = len(box)
+    words = [] if shift_words is None else [int(w) for w in np.asarray(shift_words).ravel()]
+    opt = mod.LatticeOptions(shifts=int(shifts), seed=int(seed), shift_words=words,
+                             z=[] if z is None else [int(v) for v in z],
+                             rtol=float(rtol or 0.0), atol=float(atol or 0.0), m_min=int(m_min),
+                             m_max=int(m_max or 0))
+    walk = m is None
+    if walk:
+        mod.lattice_check_walk(box, opt, float(scale))  # before any device call
+    else:
+        n = 1 << int(m) if 0 <= int(m) < 63 else 0
+        mod.lattice_check(box, int(m), opt, int(begin),
+                          max(n - int(begin), 0) if count is None else int(count), float(scale))
+    dev = _device()
+    key = (expr, d, bool(periodic), dev.index, int(grid))
+    el = _EXPR_LATTICE_CACHE.get(key)
+    if el is None:
+        el = _EXPR_LATTICE_CACHE[key] = mod.ExprLattice(expr, d, bool(periodic), dev.index,
+                                                        int(grid))
+    if walk:
+        r = el.integrate_to(box, opt, float(scale), comm)
+    else:
+        r = el.integrate(box, int(m), opt, int(begin), count, float(scale), comm)
+    return r, torch.from_numpy(np.array(r.estimates, dtype=np.float64))
 
 
 _EXPR_SCAN_CACHE: dict = {}
