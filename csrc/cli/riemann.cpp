@@ -36,6 +36,9 @@
 // to that tolerance (ExprAdaptive: Gauss-Kronrod (7, 15), bisection where the estimate misses):
 // the value, or with --json every field of the result; a warning on stderr when not converged.
 // One GPU, one rank: no sample count, rule, sweep, curve, y range or host engine goes with it.
+// With --params / --linspace and --row-rtol R and / or --row-atol T every row is integrated to
+// its own tolerance in shared rounds (ExprAdaptiveSweep): one line per row, or with --json the
+// per-row arrays and the call's fields; one warning with the number of rows not converged.
 // With --box A0:B0,A1:B1,... the expression is over x0, x1, ... and its integral over the box is
 // taken by a randomly shifted rank-1 lattice rule (ExprLattice): --m M for the rule of 2^M
 // points, or --rtol / --atol for the walk over M; the ranks split the points.
@@ -546,6 +549,117 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
   cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
   return 0;
 }
+// --expr with --params / --linspace and --row-rtol / --row-atol: every row to its own tolerance
+// in shared rounds (ExprAdaptiveSweep). One GPU, one rank. Refusals come before any device call.
+bool row_adaptive_requested(const cli::Args& a) { return a.has("row-rtol") || a.has("row-atol"); }
+
+int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
+  const std::string who = "--row-rtol / --row-atol";
+  MIINT_CHECK(!adaptive_requested(a), who + " are the per-row tolerance of a parameter sweep: "
+                                            "--rtol / --atol do not go with them");
+  for (const char* k : {"n", "rule", "running", "ya", "yb", "ny", "every", "running-out",
+                        "loopback", "box"})
+    MIINT_CHECK(!a.has(k), who + " choose the samples themselves: --" + k +
+                               " does not go with them");
+  MIINT_CHECK(a.has("params") || a.has("linspace"),
+              who + " need the rows of --params FILE or --linspace p0=LO:HI:COUNT");
+  MIINT_CHECK(a.integer("gpus", 1) <= 1, who + " run on one GPU: --gpus " + a.str("gpus", "") +
+                                             " does not go with them (the tolerances would need "
+                                             "a collective every round)");
+  MIINT_CHECK(cli::env_int("WORLD_SIZE", 1) <= 1,
+              who + " run as one rank: a rank environment (WORLD_SIZE = " +
+                  std::to_string(cli::env_int("WORLD_SIZE", 1)) + ") does not go with them");
+  MIINT_CHECK(!cli::on_cpu(a), who + " have no host engine: --device cpu does not go with them");
+  AdaptSweepOptions o;
+  o.rtol = adaptive_number(a, "row-rtol", o.rtol, false);
+  o.atol = adaptive_number(a, "row-atol", 0.0, false);
+  const double panels = adaptive_number(a, "panels", 0.0, true);
+  const double depth = adaptive_number(a, "max-depth", o.max_depth, true);
+  const double max_iv = adaptive_number(a, "max-intervals", 0.0, true);
+  const double max_total = adaptive_number(a, "max-total", static_cast<double>(o.max_total), true);
+  MIINT_CHECK(panels >= 0 && max_iv >= 0 && max_total >= 0 && std::fabs(depth) < 1e9,
+              "--panels, --max-intervals, --max-total and --max-depth must not be negative or "
+              "huge");
+  o.panels = static_cast<uint64_t>(panels);
+  o.max_depth = static_cast<int>(depth);
+  o.max_intervals = static_cast<uint64_t>(max_iv);
+  o.max_total = static_cast<uint64_t>(max_total);
+  const SweepRows sw = sweep_rows(a);
+  const AdaptSweepOptions used =
+      adapt_sweep_check(sw.rows, sw.nparams, sw.params.size(), cfg.a, cfg.b, o);
+  const std::string expr = a.str("expr", "");
+  (void)expr_adapt_sweep_source(expr, sw.nparams);  // a rejected expression: before any device call
+  MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprAdaptiveSweep es(expr, sw.nparams, 0);
+  const AdaptSweepResult r = es.integrate(sw.params, sw.rows, cfg.a, cfg.b, o);
+  const double secs = wall_seconds() - process_start_seconds();
+  uint64_t missed = 0;
+  for (uint8_t c : r.converged) missed += c ? 0 : 1;
+  if (missed)
+    std::fprintf(stderr, "riemann: not converged: %llu of %llu rows (see converged, capped, "
+                 "nonfinite and forced per row with --json)\n",
+                 static_cast<unsigned long long>(missed),
+                 static_cast<unsigned long long>(sw.rows));
+  if (!a.flag("json"))
+    for (uint64_t k = 0; k < sw.rows; ++k) {
+      std::printf("%llu", static_cast<unsigned long long>(k));
+      for (int j = 0; j < sw.nparams; ++j) std::printf(" %.17g", sw.params[k * sw.nparams + j]);
+      std::printf(" %.17g\n", r.value[k]);
+    }
+  // %.17g round-trips a finite value; a non-finite one prints as null, its bits are in value_bits
+  auto doubles = [](const std::vector<double>& v) {
+    std::string s = "[";
+    for (size_t k = 0; k < v.size(); ++k) {
+      char b[40];
+      if (std::isfinite(v[k])) std::snprintf(b, sizeof b, "%s%.17g", k ? "," : "", v[k]);
+      else std::snprintf(b, sizeof b, "%snull", k ? "," : "");
+      s += b;
+    }
+    return s + "]";
+  };
+  auto counts = [](const std::vector<uint64_t>& v) {
+    std::string s = "[";
+    for (size_t k = 0; k < v.size(); ++k)
+      s += (k ? "," : "") + std::to_string(static_cast<unsigned long long>(v[k]));
+    return s + "]";
+  };
+  auto flags = [](const std::vector<uint8_t>& v) {
+    std::string s = "[";
+    for (size_t k = 0; k < v.size(); ++k) s += std::string(k ? "," : "") + (v[k] ? "true" : "false");
+    return s + "]";
+  };
+  std::string bits = "[";
+  for (size_t k = 0; k < r.value.size(); ++k) {
+    char b[24];
+    uint64_t w = 0;
+    std::memcpy(&w, &r.value[k], sizeof w);
+    std::snprintf(b, sizeof b, "%s\"%016llx\"", k ? "," : "", static_cast<unsigned long long>(w));
+    bits += b;
+  }
+  bits += "]";
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
+      .add("rows", static_cast<double>(sw.rows)).add("nparams", sw.nparams)
+      .add("rtol", used.rtol).add("atol", used.atol)
+      .add("panels", static_cast<double>(used.panels)).add("max_depth", used.max_depth)
+      .add("max_intervals", static_cast<double>(used.max_intervals))
+      .add("max_total", static_cast<double>(used.max_total))
+      .add_raw("value", doubles(r.value)).add_raw("value_bits", bits)
+      .add_raw("err_est", doubles(r.err_est)).add_raw("resabs", doubles(r.resabs))
+      .add_raw("tol", doubles(r.tol)).add_raw("converged", flags(r.converged))
+      .add_raw("evals", counts(r.evals)).add_raw("rounds", counts(r.rounds))
+      .add_raw("intervals", counts(r.intervals)).add_raw("splits", counts(r.splits))
+      .add_raw("floor", counts(r.floor)).add_raw("forced", counts(r.forced))
+      .add_raw("nonfinite", counts(r.nonfinite)).add_raw("capped", flags(r.capped))
+      .add("not_converged", static_cast<double>(missed))
+      .add("call_rounds", static_cast<double>(r.call_rounds))
+      .add("call_evals", static_cast<double>(r.call_evals))
+      .add("peak", static_cast<double>(r.peak));
+  cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
+  return 0;
+}
+
 
 // --expr with --box A0:B0,A1:B1,...: the integral of f(x0, ..., x{d-1}) over the box by a
 // randomly shifted rank-1 lattice rule (ExprLattice). --m M: the rule of n = 2^M points; --rtol R
@@ -695,6 +809,7 @@ int run_expr_lattice(const cli::Args& a, int iters) {
 
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (row_adaptive_requested(a)) return run_expr_adaptive_sweep(a, cfg);
   if (a.has("box")) return run_expr_lattice(a, iters);
   if (adaptive_requested(a)) return run_expr_adaptive(a, cfg);
   if (a.has("ya")) return run_expr2d(a, cfg, nd, iters);
@@ -760,6 +875,8 @@ constexpr const char* kUsage =
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
     "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
     "                [--max-intervals M]]\n"
+    "               [--expr EXPR --a A --b B --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
+    "                [--row-atol T] [--panels P] [--max-depth D] [--max-intervals M] [--max-total N]]\n"
     "               [--expr EXPR --box A0:B0,A1:B1,... --m M | --rtol R [--atol T] [--m-max M]\n"
     "                [--shifts R] [--seed S] [--periodic] [--z Z0,Z1,...] [--analytic V]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
@@ -779,6 +896,15 @@ constexpr const char* kUsage =
     "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
     "  device_ms. One GPU, one rank, no host engine: refused with --n, --rule, --running, --ya,\n"
     "  --params, --linspace, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n"
+    "--row-rtol R / --row-atol T: with --params or --linspace, the integral of --expr on [A, B] for\n"
+    "  every row to the row's own tolerance max(T, R |value of the row|), the rows sharing the\n"
+    "  rounds (--panels P per row, default: 65536 / rows as a power of two, at least 16;\n"
+    "  --max-intervals M per row, default --max-total / rows; --max-total N for all rows together,\n"
+    "  default 2^22; --max-depth D). Prints 'row parameters value' lines and one warning on stderr\n"
+    "  with the number of rows not converged; --json: the per-row arrays value, value_bits, err_est,\n"
+    "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
+    "  and rows, call_rounds, call_evals, peak, device_ms. Refused with --rtol, --atol, --n, --rule,\n"
+    "  --running, --ya, --box, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n"
     "--box A0:B0,A1:B1,...: the integral of --expr over x0, x1, ... (at most 16 sides) by a randomly\n"
     "  shifted rank-1 lattice rule: --m M for n = 2^M points (built-in generating vectors for M =\n"
     "  10..26, else --z Z0,Z1,... odd and below n), --shifts R random shifts (default 16) from\n"
@@ -843,9 +969,13 @@ int main(int argc, char** argv) {
                 "--ya / --yb are the double integral of an --expr integrand over x and y");
     MIINT_CHECK(a.has("expr") || !adaptive_requested(a),
                 "--rtol / --atol are the tolerance of an --expr integrand");
-    MIINT_CHECK(adaptive_requested(a) ||
+    MIINT_CHECK(a.has("expr") || !row_adaptive_requested(a),
+                "--row-rtol / --row-atol are the per-row tolerance of an --expr parameter sweep");
+    MIINT_CHECK(adaptive_requested(a) || row_adaptive_requested(a) ||
                     !(a.has("panels") || a.has("max-depth") || a.has("max-intervals")),
                 "--panels / --max-depth / --max-intervals belong to --rtol / --atol");
+    MIINT_CHECK(row_adaptive_requested(a) || !a.has("max-total"),
+                "--max-total belongs to --row-rtol / --row-atol");
     MIINT_CHECK(a.has("expr") || !a.has("box"),
                 "--box is the box of an --expr integrand over x0, x1, ...");
     for (const char* k : {"m", "shifts", "seed", "z", "periodic", "m-max"})

@@ -480,6 +480,131 @@ class ExprAdaptive {
 };
 
 // ---------------------------------------------------------------------------------------
+// Adaptive sweeps: f(x, p0..p{nparams-1}) on a shared [a, b] for K parameter rows, each row to
+// its own tolerance max(atol, rtol |value of that row|), in shared rounds.
+//
+// Row r is treated exactly as ExprAdaptive treats its one integral: `panels` equal intervals
+// with the same edges, the same (7, 15) pair on the same node bits in the same order (the two
+// sources share miint_gk15's text), the same decisions in the same order against the row's own
+// tol = max(atol, rtol |S_acc(r) + sum_K(r)|) and the shared width W = |b - a|, the same
+// bisection, and the same cap: when the row's accepted intervals plus its next list would pass
+// max_intervals (per row) the row's round is capped, nothing of the row is split and its
+// pending K and err join its totals. Other rows do not notice.
+//
+// All rows' active intervals form one list sorted by (row, x), so a row is a contiguous segment
+// (start, length), and the active rows form a compacted list in row order. A round, over the n
+// active intervals of the na active rows (expr_adaptive_sweep.cpp):
+//
+//   miint_asweep_eval     one interval per lane: the row's parameters by the interval's row
+//                         index, then K, err, R
+//   miint_asweep_row      one wave per active row, no LDS, no barrier. sum_K: lane l chains
+//                         elements l, l + 64, ... of the segment in index order from 0.0, then
+//                         the 64-lane butterfly (xor 32, 16, ..., 1). The tolerance, then the
+//                         decision per interval in chunks of 64 in index order: a split interval
+//                         gets its rank among the row's splits (ballot and popcount, exact); the
+//                         five sums (accepted K, err, R, pending K, err) each in the order of
+//                         sum_K. Lane 0 closes the row's round: capped or not, the totals
+//                         (S_acc += accepted K, + pending K when capped, as ExprAdaptive adds
+//                         them), the counters, the row's next length
+//   miint_asweep_prefix   one workgroup: exclusive prefix over the active rows of their next
+//                         lengths (integers) -> every row's next segment start, the next list of
+//                         active rows in row order, and the record (the next total and active
+//                         count) into pinned host memory
+//   miint_asweep_scatter  one interval per lane: children (lo, c), (c, hi) at depth + 1 to slots
+//                         start(row) + 2 rank, + 1 of the other list, unless the row was capped
+//
+// Every floating-point sum of a row is formed from the row's own segment by the row's own wave,
+// in an order that is a function of the segment's length only: a row's value, err_est, resabs,
+// tol, counters and round count are bitwise the same alone, in any batch and at any position.
+// A NaN stays in its row's state. What crosses rows is integer bookkeeping. Kernels are
+// separated by launches; no workgroup waits on another and there is no floating-point atomic.
+// The host reads the record after one sync per round and stops when no row is active; the
+// per-row results are read back once after the last round.
+//
+// rows * max_intervals <= max_total (the capacity of the two lists) is checked up front and a
+// row's next list never passes its cap, so the lists cannot overflow. a > b integrates [b, a]
+// and negates every value; a == b gives K zero rows with no launch; rows == 0 an empty result.
+// Left out: the final partition, per-row ranges, multi-rank runs.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t kAdaptSweepMaxTotalLimit = 1ull << 26;
+constexpr uint64_t kAdaptSweepInitialTotal = 65536;  // rows * panels the default aims at
+constexpr uint64_t kAdaptSweepMinPanels = 16;
+
+struct AdaptSweepOptions {
+  double rtol = 1e-10, atol = 0.0;
+  uint64_t panels = 0;         // 0: adapt_sweep_default_panels(rows)
+  int max_depth = 60;
+  uint64_t max_intervals = 0;  // per row; 0: max_total / rows
+  uint64_t max_total = 1ull << 22;
+};
+struct AdaptSweepResult {
+  // per row
+  std::vector<double> value, err_est, resabs, tol;
+  std::vector<uint8_t> converged, capped;
+  std::vector<uint64_t> evals, rounds, intervals, splits, floor, forced, nonfinite;
+  // for the call
+  uint64_t call_rounds = 0;  // the maximum over rows
+  uint64_t call_evals = 0;   // the sum over rows
+  uint64_t peak = 0;         // the longest whole list
+  double device_ms = 0.0;
+  uint64_t rows() const { return value.size(); }
+};
+
+// panels = 0: the largest power of two p <= 65536 with rows * p <= 65536, at least 16.
+uint64_t adapt_sweep_default_panels(uint64_t rows);
+// The options with the two zeros resolved, after every refusal (no device needed; throws
+// naming the numbers): rows <= 2^20, nparams 0..8, param_count == rows * nparams,
+// 1 <= max_total <= 2^26, then adapt_check on the resolved panels and max_intervals (so
+// panels > max_intervals is refused there), then rows * max_intervals <= max_total.
+AdaptSweepOptions adapt_sweep_check(uint64_t rows, int nparams, uint64_t param_count, double a,
+                                    double b, const AdaptSweepOptions& opt);
+// Kernel source for f(x, p0..p{nparams-1}); a pJ at or above nparams fails in the compiler.
+std::string expr_adapt_sweep_source(const std::string& expr, int nparams);
+// hipRTC compile for gfx950 (no device needed), cached per (expression, nparams).
+std::string expr_adapt_sweep_compile(const std::string& expr, int nparams);
+
+class ExprAdaptiveSweep {
+ public:
+  ExprAdaptiveSweep(const std::string& expr, int nparams, int device = 0);
+  ExprAdaptiveSweep(const ExprAdaptiveSweep&) = delete;
+  ExprAdaptiveSweep& operator=(const ExprAdaptiveSweep&) = delete;
+  // The integrals of f(x, params[k * nparams ..]) on [a, b] for `rows` rows (params is rows x
+  // nparams, row-major; rows is explicit because nparams may be 0). Synchronous: one sync per
+  // round, one copy back of the rows' results at the end.
+  AdaptSweepResult integrate(const std::vector<double>& params, uint64_t rows, double a, double b,
+                             const AdaptSweepOptions& opt = {});
+  // Device ms per call over `iters` back-to-back calls (events around them; the rows are
+  // uploaded once, before the clock; the rounds' syncs and the host's reads are inside).
+  double time(const std::vector<double>& params, uint64_t rows, double a, double b,
+              const AdaptSweepOptions& opt, int iters);
+  const std::string& expression() const { return expr_; }
+  int nparams() const { return nparams_; }
+
+ private:
+  struct Call {
+    uint64_t rounds = 0, evals = 0, peak = 0;
+  };
+  void reserve(uint64_t max_total, uint64_t rows);
+  void upload(const std::vector<double>& params);
+  Call rounds(double lo, double hi, uint64_t rows, const AdaptSweepOptions& opt);
+  std::string expr_;
+  int nparams_, device_;
+  Stream stream_;
+  uint64_t reserved_ = 0, reserved_rows_ = 0;
+  DeviceBuffer<double> params_;
+  DeviceBuffer<double> list_[2];         // (lo, hi) pairs: 2 x max_total doubles each
+  DeviceBuffer<unsigned> depth_[2], row_[2];  // per interval: its depth and its row
+  DeviceBuffer<double> k_, err_, r_;     // per interval
+  DeviceBuffer<unsigned> rank_;          // per interval: its rank among the row's splits, or none
+  DeviceBuffer<unsigned> active_[2];     // the active rows in row order
+  DeviceBuffer<unsigned> seg_start_, seg_len_, next_len_;  // per row / per active slot
+  DeviceBuffer<unsigned long long> state_;   // 16 words per row (expr_adaptive_sweep.cpp)
+  PinnedBuffer<unsigned long long> record_;  // the next total and active count
+  Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+};
+
+// ---------------------------------------------------------------------------------------
 // Integrals over a box in up to 16 variables: f(x0, ..., x{d-1}) on [a_0, b_0] x ... by a
 // randomly shifted rank-1 lattice rule, with an error estimate from the shifts.
 //

@@ -23,6 +23,13 @@ std::string rtc_compile_cached(const std::string& src, const std::string& expr);
 // step, the lane split and the per-sample loop, each described where it is written.
 extern const char* const kRtcPrelude;
 
+// The adaptive families' shared device text (expr_adaptive.cpp): miint_f(x<sig>) for `expr`, the
+// MIINT_GK_* macros and miint_gk15(lo, hi<sig>, &k, &err, &r) on the rule's one table. `sig` is
+// "" or ", double p0, ..." and `args` the matching "" or ", p0, ...": ExprAdaptive and
+// ExprAdaptiveSweep evaluate the same fifteen nodes in the same order.
+std::string adapt_rule_source(const std::string& expr, const std::string& sig,
+                              const std::string& args);
+
 // A loaded code object and its kernels. The destructor selects the device, drains the owning
 // object's stream and unloads: declare it as the owner's LAST member, after the Stream, the
 // buffers and the events, so that member order destroys it first (nothing a kernel may still

@@ -1095,6 +1095,105 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprAdaptive::expression);
 
+  // adaptive sweeps: f(x, p0..p7) for K rows, each row to its own tolerance, in shared rounds
+  m.attr("ADAPT_SWEEP_MAX_TOTAL_LIMIT") = kAdaptSweepMaxTotalLimit;
+  m.attr("ADAPT_SWEEP_INITIAL_TOTAL") = kAdaptSweepInitialTotal;
+  m.attr("ADAPT_SWEEP_MIN_PANELS") = kAdaptSweepMinPanels;
+  py::class_<AdaptSweepOptions>(m, "AdaptSweepOptions",
+                                "tolerances and bounds of an adaptive sweep (0: derived)")
+      .def(py::init([](double rtol, double atol, uint64_t panels, int max_depth,
+                       uint64_t max_intervals, uint64_t max_total) {
+             AdaptSweepOptions o;
+             o.rtol = rtol;
+             o.atol = atol;
+             o.panels = panels;
+             o.max_depth = max_depth;
+             o.max_intervals = max_intervals;
+             o.max_total = max_total;
+             return o;
+           }),
+           py::arg("rtol") = 1e-10, py::arg("atol") = 0.0, py::arg("panels") = 0,
+           py::arg("max_depth") = 60, py::arg("max_intervals") = 0,
+           py::arg("max_total") = uint64_t(1) << 22)
+      .def_readwrite("rtol", &AdaptSweepOptions::rtol)
+      .def_readwrite("atol", &AdaptSweepOptions::atol)
+      .def_readwrite("panels", &AdaptSweepOptions::panels)
+      .def_readwrite("max_depth", &AdaptSweepOptions::max_depth)
+      .def_readwrite("max_intervals", &AdaptSweepOptions::max_intervals)
+      .def_readwrite("max_total", &AdaptSweepOptions::max_total);
+  {
+    // per-row fields as numpy arrays (copies); the call's fields as numbers
+    auto f64 = [](const std::vector<double>& v) {
+      return py::array_t<double>(static_cast<py::ssize_t>(v.size()), v.data());
+    };
+    auto u64 = [](const std::vector<uint64_t>& v) {
+      return py::array_t<uint64_t>(static_cast<py::ssize_t>(v.size()), v.data());
+    };
+    auto flag = [](const std::vector<uint8_t>& v) {
+      py::array_t<bool> out(static_cast<py::ssize_t>(v.size()));
+      for (size_t i = 0; i < v.size(); ++i) out.mutable_data()[i] = v[i] != 0;
+      return out;
+    };
+    using R = AdaptSweepResult;
+    py::class_<R>(m, "AdaptSweepResult",
+                  "per-row arrays (value ... capped) and the call's rounds, evals, peak, device_ms")
+        .def(py::init<>())
+        .def_property_readonly("value", [f64](const R& r) { return f64(r.value); })
+        .def_property_readonly("err_est", [f64](const R& r) { return f64(r.err_est); })
+        .def_property_readonly("resabs", [f64](const R& r) { return f64(r.resabs); })
+        .def_property_readonly("tol", [f64](const R& r) { return f64(r.tol); })
+        .def_property_readonly("converged", [flag](const R& r) { return flag(r.converged); })
+        .def_property_readonly("capped", [flag](const R& r) { return flag(r.capped); })
+        .def_property_readonly("evals", [u64](const R& r) { return u64(r.evals); })
+        .def_property_readonly("rounds", [u64](const R& r) { return u64(r.rounds); })
+        .def_property_readonly("intervals", [u64](const R& r) { return u64(r.intervals); })
+        .def_property_readonly("splits", [u64](const R& r) { return u64(r.splits); })
+        .def_property_readonly("floor", [u64](const R& r) { return u64(r.floor); })
+        .def_property_readonly("forced", [u64](const R& r) { return u64(r.forced); })
+        .def_property_readonly("nonfinite", [u64](const R& r) { return u64(r.nonfinite); })
+        .def_property_readonly("rows", &R::rows)
+        .def_readonly("call_rounds", &R::call_rounds)
+        .def_readonly("call_evals", &R::call_evals)
+        .def_readonly("peak", &R::peak)
+        .def_readonly("device_ms", &R::device_ms);
+  }
+  m.def("adapt_sweep_default_panels", &adapt_sweep_default_panels, py::arg("rows"),
+        "the panels a sweep of `rows` rows starts from unless told");
+  m.def("adapt_sweep_check", &adapt_sweep_check, py::arg("rows"), py::arg("nparams"),
+        py::arg("param_count"), py::arg("a"), py::arg("b"), py::arg("options"),
+        "raise, naming the numbers, unless ExprAdaptiveSweep takes the call; returns the options "
+        "with panels = 0 and max_intervals = 0 resolved");
+  m.def("expr_adapt_sweep_source", &expr_adapt_sweep_source, py::arg("expr"), py::arg("nparams"),
+        "source of the adaptive sweep kernels generated for f(x, p0..p{nparams-1})");
+  m.def("expr_adapt_sweep_compile", compiled(&expr_adapt_sweep_compile), py::arg("expr"),
+        py::arg("nparams"),
+        "compile the adaptive sweep kernels for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprAdaptiveSweep>(m, "ExprAdaptiveSweep",
+                                "f(x, p0..p7) for K rows, each to a requested tolerance (hipRTC)")
+      .def(py::init<const std::string&, int, int>(), py::arg("expr"), py::arg("nparams"),
+           py::arg("device") = 0)
+      .def("integrate",
+           [](ExprAdaptiveSweep& e, const ParamRows& params, double a, double b,
+              const AdaptSweepOptions& o) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             py::gil_scoped_release nogil;
+             return e.integrate(p, rows, a, b, o);
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"),
+           py::arg("options") = AdaptSweepOptions())
+      .def("time",
+           [](ExprAdaptiveSweep& e, const ParamRows& params, double a, double b,
+              const AdaptSweepOptions& o, int iters) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             py::gil_scoped_release nogil;
+             return e.time(p, rows, a, b, o, iters);
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"), py::arg("options"), py::arg("iters"))
+      .def_property_readonly("expression", &ExprAdaptiveSweep::expression)
+      .def_property_readonly("nparams", &ExprAdaptiveSweep::nparams);
+
   // integrals over a box in up to 16 variables: randomly shifted rank-1 lattice rules
   m.attr("LATTICE_MAX_DIM") = kLatticeMaxDim;
   m.attr("LATTICE_MIN_M") = kLatticeMinM;

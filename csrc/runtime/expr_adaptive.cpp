@@ -110,8 +110,9 @@ void adapt_check(double a, double b, const AdaptOptions& o) {
               what + "max_depth = " + std::to_string(o.max_depth) + " must be 0..200");
 }
 
-std::string expr_adapt_source(const std::string& expr) {
-  detail::expr_check_named(expr);
+namespace detail {
+std::string adapt_rule_source(const std::string& expr, const std::string& sig,
+                              const std::string& args) {
   // the table, printed: the centre, then a pair of nodes per line (the even ones are Gauss nodes)
   std::string rule = "  MIINT_GK_CENTRE(" + hex(kGkWeight[0]) + ", " + hex(kGaussWeight[0]) + ")\n";
   for (int j = 1; j < 8; ++j) {
@@ -121,21 +122,21 @@ std::string expr_adapt_source(const std::string& expr) {
     else
       rule += "  MIINT_GK_PAIR(" + hex(kGkNode[j]) + ", " + hex(kGkWeight[j]) + ")\n";
   }
-  return std::string(detail::kRtcPrelude) + R"(
-__device__ __forceinline__ double miint_f(double x) { return ()" + expr + R"(); }
+  return R"(
+__device__ __forceinline__ double miint_f(double x)" + sig + R"() { return ()" + expr + R"(); }
 
 // The (7, 15) pair on [lo, hi]: f at the centre and at the seven pairs fma(hw, -+t, c), from
 // the centre outwards, the three sums carried by fma in that order.
 #define MIINT_GK_CENTRE(wk, wg) \
-  { const double f0 = miint_f(c); sk = wk * f0; sg = wg * f0; sa = wk * fabs(f0); }
+  { const double f0 = miint_f(c)" + args + R"(); sk = wk * f0; sg = wg * f0; sa = wk * fabs(f0); }
 #define MIINT_GK_PAIR(t, wk)                                                  \
-  { const double f1 = miint_f(fma(hw, -t, c)), f2 = miint_f(fma(hw, t, c));   \
+  { const double f1 = miint_f(fma(hw, -t, c))" + args + R"(), f2 = miint_f(fma(hw, t, c))" + args + R"();   \
     sk = fma(wk, f1 + f2, sk); sa = fma(wk, fabs(f1) + fabs(f2), sa); }
 #define MIINT_GK_GAUSS_PAIR(t, wk, wg)                                        \
-  { const double f1 = miint_f(fma(hw, -t, c)), f2 = miint_f(fma(hw, t, c));   \
+  { const double f1 = miint_f(fma(hw, -t, c))" + args + R"(), f2 = miint_f(fma(hw, t, c))" + args + R"();   \
     sk = fma(wk, f1 + f2, sk); sa = fma(wk, fabs(f1) + fabs(f2), sa);         \
     sg = fma(wg, f1 + f2, sg); }
-__device__ __forceinline__ void miint_gk15(double lo, double hi, double* k, double* err,
+__device__ __forceinline__ void miint_gk15(double lo, double hi)" + sig + R"(, double* k, double* err,
                                            double* r) {
 #pragma clang fp contract(off)  // K and G are rounded before they are compared
   const double hw = 0.5 * (hi - lo), c = lo + hw;
@@ -145,7 +146,13 @@ __device__ __forceinline__ void miint_gk15(double lo, double hi, double* k, doub
   *err = fabs(kv - gv);
   *r = hw * sa;
 }
+)";
+}
+}  // namespace detail
 
+std::string expr_adapt_source(const std::string& expr) {
+  detail::expr_check_named(expr);
+  return std::string(detail::kRtcPrelude) + detail::adapt_rule_source(expr, "", "") + R"(
 // st[0..7] as doubles: S_acc, E_acc, R_acc, tol, sum_K; st[8..15]: accepted, splits, floor,
 // forced, nonfinite, next, capped, base (the intervals accepted before this round).
 #define MIINT_ST_D(st, i) (((double*)(st))[i])

@@ -23,7 +23,10 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     ``ops.kernels.riemann_expr2d``, ``riemann --expr ... --ya AY --yb BY``), and its
     integral to a requested tolerance with an error estimate, the samples placed where
     the integrand needs them (``integrate_expr_adaptive``, ``ops.kernels.quad_expr``,
-    ``riemann --expr ... --rtol R``), and its integral over a box in up to 16 variables by
+    ``riemann --expr ... --rtol R``), and the same for f(x, p) over K parameter rows, each
+    row to its own tolerance in shared rounds (``integrate_expr_adaptive_sweep``,
+    ``ops.kernels.quad_expr_sweep``, ``riemann --expr ... --params FILE --row-rtol R``), and
+    its integral over a box in up to 16 variables by
     a randomly shifted lattice rule (``integrate_expr_nd``, ``ops.kernels.lattice_expr``,
     ``riemann --expr ... --box 0:1,0:1,0:3 --m 20``).
 
@@ -40,5 +43,6 @@ from .integrate import SweepResult, integrate_expr_sweep  # noqa: F401
 from .integrate import RunningResult, integrate_expr_running  # noqa: F401
 from .integrate import integrate_expr2d  # noqa: F401
 from .integrate import AdaptiveResult, integrate_expr_adaptive  # noqa: F401
+from .integrate import AdaptiveSweepResult, integrate_expr_adaptive_sweep  # noqa: F401
 from .integrate import LatticeResult, integrate_expr_nd  # noqa: F401
 from .models import integrands  # noqa: F401

@@ -191,11 +191,15 @@ def cmd_integrate(a) -> int:
     if a.expr:  # any f(x): compiled at run time with hipRTC (ops.kernels.riemann_expr)
         from .ops import kernels
 
+        lo = 0.0 if a.a is None else a.a
+        hi = 1.0 if a.b is None else a.b
+        if a.row_rtol is not None or a.row_atol is not None:
+            return _integrate_adaptive_sweep(a, lo, hi)
+        if a.max_total is not None:
+            raise SystemExit("integrate: --max-total belongs to --row-rtol / --row-atol")
         if a.box:
             return _integrate_lattice(a)
         _no_lattice_flags(a)
-        lo = 0.0 if a.a is None else a.a
-        hi = 1.0 if a.b is None else a.b
         if a.rtol is not None or a.atol is not None:
             return _integrate_adaptive(a, lo, hi)
         if a.panels is not None or a.max_depth is not None or a.max_intervals is not None:
@@ -256,6 +260,9 @@ def cmd_integrate(a) -> int:
     if a.box:
         raise SystemExit("integrate: --box is the box of an --expr integrand over x0, x1, ...")
     _no_lattice_flags(a)
+    if a.row_rtol is not None or a.row_atol is not None or a.max_total is not None:
+        raise SystemExit("integrate: --row-rtol / --row-atol are the per-row tolerance of an "
+                         "--expr parameter sweep")
     if (a.rtol is not None or a.atol is not None or a.panels is not None
             or a.max_depth is not None or a.max_intervals is not None):
         raise SystemExit("integrate: --rtol / --atol and their bounds are the tolerance of an "
@@ -370,6 +377,64 @@ def _integrate_adaptive(a, lo: float, hi: float) -> int:
                                                  "little")
     if a.analytic is not None:
         rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
+    print(json.dumps(rec))
+    return 0
+
+
+def _integrate_adaptive_sweep(a, lo: float, hi: float) -> int:
+    """integrate --expr E --params FILE | --linspace SPEC --row-rtol R / --row-atol T: every row
+    to its own tolerance in shared rounds (one GPU, one rank). Whatever belongs to another mode is
+    refused before anything runs."""
+    import os
+
+    from . import integrate_expr_adaptive_sweep
+    from ._native import native
+
+    who = "--row-rtol / --row-atol"
+    if a.rtol is not None or a.atol is not None:
+        raise SystemExit(f"integrate: {who} are the per-row tolerance of a parameter sweep: "
+                         "--rtol / --atol do not go with them")
+    given = {"--n": a.n is not None, "--rule": a.rule is not None, "--ya": a.ya is not None,
+             "--yb": a.yb is not None, "--ny": a.ny is not None, "--box": bool(a.box)}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: {who} choose the samples themselves: {flag} does not "
+                             "go with them")
+    _no_lattice_flags(a)
+    if not (a.params or a.linspace):
+        raise SystemExit(f"integrate: {who} need the rows of --params FILE or --linspace "
+                         "p0=LO:HI:COUNT")
+    if a.params and a.linspace:
+        raise SystemExit("integrate: give --params FILE or --linspace, not both")
+    if a.device == "cpu" or a.backend != "hip":
+        which = "--device cpu" if a.device == "cpu" else f"--backend {a.backend}"
+        raise SystemExit(f"integrate: {who} have no host engine: {which} does not go with them")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"integrate: {who} run as one rank: a rank environment "
+                         f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
+    opts = {k: v for k, v in (("rtol", a.row_rtol), ("atol", a.row_atol), ("panels", a.panels),
+                              ("max_depth", a.max_depth), ("max_intervals", a.max_intervals),
+                              ("max_total", a.max_total)) if v is not None}
+    m = native()
+    try:
+        rows = m.load_param_rows(a.params) if a.params else m.linspace_param_rows(a.linspace)
+        r = integrate_expr_adaptive_sweep(a.expr, rows, lo, hi, **opts)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    missed = int((~r.converged).sum())
+    if missed:
+        print(f"integrate: not converged: {missed} of {len(r.value)} rows (see converged, capped, "
+              "nonfinite and forced per row with --json)", file=sys.stderr)
+    if not a.json:
+        for k, (row, v) in enumerate(zip(rows, r.value)):
+            print(k, " ".join(f"{p:.17g}" for p in row), f"{v:.17g}")
+        return 0
+    pack = __import__("struct").pack
+    rec = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.as_dict().items()}
+    rec["rows"] = len(r.value)
+    rec["not_converged"] = missed
+    rec["value_bits"] = ["%016x" % int.from_bytes(pack("<d", float(v)), "little")
+                         for v in r.value]
     print(json.dumps(rec))
     return 0
 
@@ -495,6 +560,13 @@ def main(argv=None) -> int:
                     "intervals to start from (65536)")
     ig.add_argument("--max-depth", type=int, default=None, help="bisections of one interval (60)")
     ig.add_argument("--max-intervals", type=int, default=None, help="intervals in all (2^22)")
+    ig.add_argument("--row-rtol", type=float, default=None, help="with --expr and --params / "
+                    "--linspace: every row to its own tolerance max(row-atol, row-rtol |value of "
+                    "the row|), the rows sharing the rounds (one GPU, one rank); --panels and "
+                    "--max-intervals are then per row")
+    ig.add_argument("--row-atol", type=float, default=None)
+    ig.add_argument("--max-total", type=int, default=None, help="--row-rtol / --row-atol: "
+                    "intervals of all rows together (2^22)")
     ig.add_argument("--box", default="", help="with --expr over x0, x1, ...: A0:B0,A1:B1,..., the "
                     "integral over the box by a randomly shifted lattice rule (--m M, or --rtol / "
                     "--atol for the walk over M)")

@@ -600,6 +600,77 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
 
 
 @dataclasses.dataclass
+class AdaptiveSweepResult:
+    """Per row (numpy arrays of K entries, fields as in ``AdaptiveResult``), then the call."""
+    value: "np.ndarray"
+    err_est: "np.ndarray"
+    resabs: "np.ndarray"
+    tol: "np.ndarray"          # the row's last tolerance, max(atol, rtol * |its value so far|)
+    converged: "np.ndarray"    # bool
+    evals: "np.ndarray"
+    rounds: "np.ndarray"       # the last round in which the row had an active interval
+    intervals: "np.ndarray"
+    splits: "np.ndarray"
+    floor: "np.ndarray"
+    forced: "np.ndarray"
+    nonfinite: "np.ndarray"
+    capped: "np.ndarray"       # bool: the row's partition would have passed max_intervals
+    call_rounds: int           # the maximum over rows
+    call_evals: int            # the sum over rows
+    peak: int                  # the longest whole list
+    device_ms: float           # the rounds (hip) or the model's run (cpu), in ms
+    expr: str
+    a: float
+    b: float
+    backend: str
+
+    def as_dict(self) -> dict:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+
+
+_ADAPT_SWEEP_CALL_FIELDS = ("call_rounds", "call_evals", "peak")
+
+
+def integrate_expr_adaptive_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
+                                  atol: float = 0.0, panels: int = 0, max_depth: int = 60,
+                                  max_intervals: int = 0, max_total: int = 1 << 22,
+                                  backend: str = "hip") -> AdaptiveSweepResult:
+    """The integrals of f(x, p0, ..., p{nparams-1}) on a shared [a, b] for the K rows of
+    ``params`` (K x nparams), each row to its own tolerance max(atol, rtol * |its value|), with
+    its own error estimate, ``converged`` flag and counters; the rows share the rounds, and a
+    row's result does not depend on the rows that ride along. ``panels`` and ``max_intervals``
+    are per row (0: derived), ``max_total`` bounds all rows' intervals together.
+    ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr_sweep``),
+    one GPU. ``backend="cpu"``: the numpy model (``utils.adaptive_quad.adaptive_sweep_model``)
+    on ``expr_torch``'s subset of expressions; needs no GPU. One rank, one shared finite
+    range."""
+    from .utils.adaptive_quad import SWEEP_ROW_FIELDS, adaptive_sweep_model
+
+    a, b = float(a), float(b)
+    opts = dict(rtol=rtol, atol=atol, panels=int(panels), max_depth=int(max_depth),
+                max_intervals=int(max_intervals), max_total=int(max_total))
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr_sweep(expr, params, a, b, **opts)[0]
+        fields = {k: getattr(r, k) for k in SWEEP_ROW_FIELDS + _ADAPT_SWEEP_CALL_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        def f(x, *row):
+            names = {f"p{j}": torch.tensor(float(v), dtype=torch.float64)
+                     for j, v in enumerate(row)}
+            return expr_torch(expr, torch.from_numpy(x), names=names).numpy()
+
+        t0 = time.perf_counter()
+        r = adaptive_sweep_model(f, params, a, b, **opts)
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in SWEEP_ROW_FIELDS + _ADAPT_SWEEP_CALL_FIELDS}
+    else:
+        raise ValueError("integrate_expr_adaptive_sweep backend must be 'hip' or 'cpu'")
+    return AdaptiveSweepResult(**fields, device_ms=ms, expr=expr, a=a, b=b, backend=backend)
+
+
+@dataclasses.dataclass
 class LatticeResult:
     value: float
     err_est: float          # one standard error over the shifts, not a bound; inf for one shift

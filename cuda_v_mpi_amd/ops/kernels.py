@@ -514,6 +514,44 @@ def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 
     return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
 
 
+_EXPR_ADAPT_SWEEP_CACHE: dict = {}
+
+
+def quad_expr_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
+                    atol: float = 0.0, panels: int = 0, max_depth: int = 60,
+                    max_intervals: int = 0, max_total: int = 1 << 22):
+    """The integrals of f(x, p0, ..., p{nparams-1}) on [a, b] for K parameter rows, each row to
+    its own tolerance max(atol, rtol * |value of that row|), in shared rounds: ``params`` is
+    K x nparams as for ``riemann_expr_sweep``. Row by row the rule is ``quad_expr``'s, and a
+    row's result is bitwise the same alone, in any batch and at any position
+    (csrc/runtime/expr_adaptive_sweep.cpp). ``panels`` and ``max_intervals`` are per row
+    (0: derived from the row count and ``max_total``, the capacity of the lists for all rows
+    together). One hipRTC compile per (expression, nparams), cached with its module per device.
+    Returns ``(result, values, err_est, converged)``: the native AdaptSweepResult (per-row
+    arrays value, err_est, resabs, tol, converged, evals, rounds, intervals, splits, floor,
+    forced, nonfinite, capped; for the call call_rounds, call_evals, peak, device_ms) and the
+    first three of its per-row arrays as 1-D device tensors (fp64, fp64, bool). No rows: empty
+    results, nothing compiled or launched."""
+    m = native()
+    p = _param_rows(params)
+    rows, nparams = p.shape
+    opt = m.AdaptSweepOptions(float(rtol), float(atol), int(panels), int(max_depth),
+                              int(max_intervals), int(max_total))
+    m.adapt_sweep_check(int(rows), int(nparams), int(p.size), float(a), float(b), opt)
+    dev = _device()
+    if rows == 0:
+        r = m.AdaptSweepResult()
+    else:
+        key = (expr, int(nparams), dev.index)
+        es = _EXPR_ADAPT_SWEEP_CACHE.get(key)
+        if es is None:
+            es = _EXPR_ADAPT_SWEEP_CACHE[key] = m.ExprAdaptiveSweep(expr, int(nparams), dev.index)
+        r = es.integrate(p, float(a), float(b), opt)
+    return (r, torch.as_tensor(r.value, dtype=torch.float64).to(dev),
+            torch.as_tensor(r.err_est, dtype=torch.float64).to(dev),
+            torch.as_tensor(r.converged, dtype=torch.bool).to(dev))
+
+
 _EXPR_LATTICE_CACHE: dict = {}
 
 

@@ -133,3 +133,99 @@ def adaptive_model(f, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0
                lo=plo, hi=phi)
     out["converged"] = bool(e_acc <= tol and not out["capped"] and out["nonfinite"] == 0)
     return out
+
+
+# ------------------------------------------------------------------ sweeps: K rows of f(x, p)
+SWEEP_DEFAULTS = dict(rtol=1e-10, atol=0.0, panels=0, max_depth=60, max_intervals=0,
+                      max_total=1 << 22)
+SWEEP_MAX_ROWS = 1 << 20
+SWEEP_MAX_PARAMS = 8
+SWEEP_INITIAL_TOTAL = 65536
+SWEEP_MIN_PANELS = 16
+
+
+def sweep_default_panels(rows: int) -> int:
+    """``panels = 0``: the largest power of two p <= 65536 with rows * p <= 65536, at least 16."""
+    p = DEFAULTS["panels"]
+    while p > SWEEP_MIN_PANELS and rows * p > SWEEP_INITIAL_TOTAL:
+        p >>= 1
+    return p
+
+
+def check_sweep_options(rows: int, nparams: int, param_count: int, a: float, b: float,
+                        rtol: float = 1e-10, atol: float = 0.0, panels: int = 0,
+                        max_depth: int = 60, max_intervals: int = 0,
+                        max_total: int = 1 << 22) -> dict:
+    """The refusals of ``adapt_sweep_check``, with its wording; returns ``panels`` and
+    ``max_intervals`` with their zeros resolved."""
+    what = "adaptive sweep: "
+    if not 0 <= rows <= SWEEP_MAX_ROWS:
+        raise ValueError(f"{what}rows = {rows} must be 0..2^20")
+    if not 0 <= nparams <= SWEEP_MAX_PARAMS:
+        raise ValueError(f"{what}nparams = {nparams} must be 0..{SWEEP_MAX_PARAMS}")
+    if param_count != rows * nparams:
+        raise ValueError(f"{what}{param_count} parameter values for {rows} rows of {nparams}")
+    if not 1 <= max_total <= 1 << 26:
+        raise ValueError(f"{what}max_total = {max_total} must be 1..2^26")
+    k = max(rows, 1)
+    if max_intervals == 0:
+        max_intervals = max_total // k
+    if panels == 0:
+        panels = sweep_default_panels(k)
+    if not 1 <= panels <= max_intervals:
+        raise ValueError(f"{what}panels = {panels} must be 1..max_intervals = {max_intervals} "
+                         "(per row)")
+    if max_intervals > max_total // k:
+        raise ValueError(f"{what}rows * max_intervals = {rows} * {max_intervals} passes "
+                         f"max_total = {max_total}")
+    check_options(a, b, rtol, atol, panels, max_depth, max_intervals)
+    return dict(panels=panels, max_intervals=max_intervals)
+
+
+SWEEP_ROW_FIELDS = ("value", "err_est", "resabs", "tol", "converged", "evals", "rounds",
+                    "intervals", "splits", "floor", "forced", "nonfinite", "capped")
+
+
+def adaptive_sweep_model(f, params, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
+                         panels: int = 0, max_depth: int = 60, max_intervals: int = 0,
+                         max_total: int = 1 << 22) -> dict:
+    """The integrals of f(x, *row) on [a, b] for every row of ``params`` (K x nparams) by the
+    rounds of ExprAdaptiveSweep. A row's result does not depend on the rows that ride along, so
+    this is ``adaptive_model`` row by row on the resolved options. Returns the per-row fields of
+    AdaptSweepResult as arrays, ``peak_row`` (each row's longest list), and for the call
+    ``call_rounds`` (the maximum), ``call_evals`` (the sum) and ``peak`` (the longest whole
+    list: rows share rounds, so round t holds every row's t-th list)."""
+    p = np.asarray(params, dtype=np.float64)
+    if p.ndim == 1 and p.size == 0:
+        p = p.reshape(0, 0)
+    if p.ndim != 2:
+        raise ValueError("params must be K rows of nparams numbers (2-D)")
+    rows, nparams = p.shape
+    a, b = float(a), float(b)
+    res = check_sweep_options(rows, nparams, p.size, a, b, rtol, atol, panels, max_depth,
+                              max_intervals, max_total)
+    runs = []
+    sizes: dict = {}
+    for row in p:
+        def frow(x, row=row):
+            return f(x, *row)
+
+        def counted(x, key=len(runs)):
+            sizes.setdefault(key, []).append(x.shape[0])
+            return frow(x)
+
+        runs.append(adaptive_model(counted, a, b, rtol=rtol, atol=atol, panels=res["panels"],
+                                   max_depth=max_depth, max_intervals=res["max_intervals"]))
+    out = {}
+    kinds = dict(converged=bool, capped=bool, value=np.float64, err_est=np.float64,
+                 resabs=np.float64, tol=np.float64)
+    for key in SWEEP_ROW_FIELDS:
+        out[key] = np.array([r[key] for r in runs], dtype=kinds.get(key, np.int64))
+    out["peak_row"] = np.array([r["peak"] for r in runs], dtype=np.int64)
+    depth = max((len(v) for v in sizes.values()), default=0)
+    whole = [sum(v[t] for v in sizes.values() if t < len(v)) for t in range(depth)]
+    out["call_rounds"] = int(out["rounds"].max()) if rows else 0
+    out["call_evals"] = int(out["evals"].sum())
+    out["peak"] = max(whole, default=0)
+    out.update(res)
+    return out
