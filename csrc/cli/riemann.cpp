@@ -36,6 +36,8 @@
 // to that tolerance (ExprAdaptive: Gauss-Kronrod (7, 15), bisection where the estimate misses):
 // the value, or with --json every field of the result; a warning on stderr when not converged.
 // One GPU, one rank: no sample count, rule, sweep, curve, y range or host engine goes with it.
+// With a tolerance, --a and --b also take inf, +inf, -inf and infinity (miint/expr.hpp, AdaptRange);
+// without one an infinite end is refused.
 // With --params / --linspace and --row-rtol R and / or --row-atol T every row is integrated to
 // its own tolerance in shared rounds (ExprAdaptiveSweep): one line per row, or with --json the
 // per-row arrays and the call's fields; one warning with the number of rows not converged.
@@ -511,6 +513,7 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
   o.panels = static_cast<uint64_t>(panels);
   o.max_depth = static_cast<int>(depth);
   o.max_intervals = static_cast<uint64_t>(max_iv);
+  o.unbounded = true;  // an infinity here was typed: --a -inf, --b inf
   adapt_check(cfg.a, cfg.b, o);
   const std::string expr = a.str("expr", "");
   (void)expr_adapt_source(expr);  // a rejected expression: before any device call
@@ -535,7 +538,8 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
       .add("intervals", static_cast<double>(r.intervals))
       .add("splits", static_cast<double>(r.splits)).add("floor", static_cast<double>(r.floor))
       .add("forced", static_cast<double>(r.forced))
-      .add("nonfinite", static_cast<double>(r.nonfinite)).add("capped", r.capped);
+      .add("nonfinite", static_cast<double>(r.nonfinite)).add("capped", r.capped)
+      .add("range", r.range);
   // %.17g round-trips a finite value; a non-finite one prints as null, its bits are here
   char bits[24];
   uint64_t w = 0;
@@ -584,6 +588,7 @@ int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
   o.max_depth = static_cast<int>(depth);
   o.max_intervals = static_cast<uint64_t>(max_iv);
   o.max_total = static_cast<uint64_t>(max_total);
+  o.unbounded = true;  // an infinity here was typed: --a -inf, --b inf
   const SweepRows sw = sweep_rows(a);
   const AdaptSweepOptions used =
       adapt_sweep_check(sw.rows, sw.nparams, sw.params.size(), cfg.a, cfg.b, o);
@@ -655,7 +660,7 @@ int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
       .add("not_converged", static_cast<double>(missed))
       .add("call_rounds", static_cast<double>(r.call_rounds))
       .add("call_evals", static_cast<double>(r.call_evals))
-      .add("peak", static_cast<double>(r.peak));
+      .add("peak", static_cast<double>(r.peak)).add("range", r.range);
   cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
   return 0;
 }
@@ -896,6 +901,13 @@ constexpr const char* kUsage =
     "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
     "  device_ms. One GPU, one rank, no host engine: refused with --n, --rule, --running, --ya,\n"
     "  --params, --linspace, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n"
+    "  A and B may be inf, +inf, -inf or infinity (any case): (A, inf), (-inf, B) and (-inf, inf)\n"
+    "  are mapped onto t in (0, 1] by x = A + (1 - t) / t, x = B - (1 - t) / t, or both halves at\n"
+    "  once, and the rounds bisect t; --json adds range: finite, upper, lower or both. There\n"
+    "  resabs is the integral of |f(x) + f(-x)| over (0, inf) for (-inf, inf). A singularity at the\n"
+    "  finite end (exp(-x)/sqrt(x) on (0, inf)) ends as nonfinite: split it at 1; an oscillatory\n"
+    "  tail (sin(x)/x) does not converge, and the run says so. The same holds with --row-rtol.\n"
+    "  An infinite A or B without --rtol / --atol / --row-rtol / --row-atol is refused.\n"
     "--row-rtol R / --row-atol T: with --params or --linspace, the integral of --expr on [A, B] for\n"
     "  every row to the row's own tolerance max(T, R |value of the row|), the rows sharing the\n"
     "  rounds (--panels P per row, default: 65536 / rows as a power of two, at least 16;\n"
@@ -931,6 +943,11 @@ int main(int argc, char** argv) {
     if (f == Integrand::kTable) hi = static_cast<double>(prof.size() - 1);
     lo = a.num("a", lo);
     hi = a.num("b", hi);
+    MIINT_CHECK((std::isfinite(lo) && std::isfinite(hi)) || std::isnan(lo) || std::isnan(hi) ||
+                    (a.has("expr") && (adaptive_requested(a) || row_adaptive_requested(a))),
+                "--a " + a.str("a", "") + " --b " + a.str("b", "") + ": an infinite range needs "
+                "--expr with --rtol / --atol or --row-rtol / --row-atol (the fixed rules have no "
+                "such range)");
     const double nd = a.num("n", 1e9);  // riemann.cpp:10 STEPS
     const auto n = static_cast<uint64_t>(nd);
     const int iters = static_cast<int>(a.integer("iters", 1));

@@ -419,11 +419,52 @@ void gk15_abscissae(double lo, double hi, double* x15);
 // the same time for exp(-x*x) and 1.0/sqrt(x) (profiles/r21/expr_adaptive.md).
 constexpr uint64_t kAdaptDefaultPanels = 65536;
 
+// ---------------------------------------------------------------------------------------
+// Infinite and half-infinite ranges (opt-in: AdaptOptions::unbounded, AdaptSweepOptions::
+// unbounded). QUADPACK's qagi map onto t in (0, 1]: infinity lands at t = 0, where doubles are
+// densest and where the (7, 15) pair never puts a node. With
+//   q = (1.0 - t) / t
+// the rounds integrate g over t in [0, 1] instead of f over x:
+//   (a, +inf), a finite   "upper"   x = a + q    g(t) = f(x) / (t * t)
+//   (-inf, b), b finite   "lower"   x = b - q    g(t) = f(x) / (t * t)
+//   (-inf, +inf)          "both"                 g(t) = (f(q) + f(-q)) / (t * t)
+// q, x and g are formed in exactly this order, every operation rounded on its own (contraction
+// off); f itself is compiled as for a finite range. The rounds are the finite rule's on [0, 1]
+// with W = 1: the same panels, init edges, decision order, caps and counters; only the
+// per-interval eval kernel has a twin per kind (miint_adapt_eval_upper / _lower / _both,
+// miint_asweep_eval_upper / ...), generated into a second source that is compiled and loaded at
+// an object's first unbounded call. So err_est, resabs and tol are those of g: resabs is the
+// rule's integral of |g|, which for "both" is that of |f(x) + f(-x)| over (0, inf), not of |f|
+// over the axis. The partition (intervals_out) is the partition of [0, 1] in t, ascending,
+// whatever the order of a and b: it is what the kernels bisected; adapt_range_map gives the x.
+// a = +inf with b finite, and the other swapped forms, negate the value as a > b does; a == b
+// gives 0 with no launch, for infinite values too (range "finite"). NaN ends are refused, and
+// so are finite ends whose b - a overflows. With `unbounded` false every check and message is
+// that of the finite rule, and with it true finite ends run the finite path bit for bit: an
+// infinity that reaches this layer from an overflowed computation is still caught, one that a
+// caller typed (the CLIs and the integrate_* functions set the flag themselves) is not.
+// Limits: an integrable singularity at the finite end sits at t = 1, where nodes soon round
+// onto the end (exp(-x)/sqrt(x) on (0, inf) reports `nonfinite`: split it into a finite call on
+// [0, 1] and (1, inf)); oscillatory tails such as sin(x)/x do not converge, and the run says so.
+// ---------------------------------------------------------------------------------------
+enum class AdaptRange { kFinite = 0, kUpper = 1, kLower = 2, kBoth = 3 };
+// "finite", "upper", "lower", "both".
+const char* adapt_range_name(AdaptRange kind);
+// The kind of the range between a and b in either order (a == b and NaN ends: kFinite).
+AdaptRange adapt_range(double a, double b);
+// The map's three lines on the host, rounded as on the device, for n values of t: x[i] and the
+// divisor jac[i] = t * t (g = f(x) / jac), and for kBoth x[i] = q, x2[i] = -q (g = (f(x) +
+// f(x2)) / jac); x2 may be null otherwise. kFinite: x = t, jac = 1. The end used is the finite
+// one of a, b. The numpy model evaluates f at these bits.
+void adapt_range_map(double a, double b, const double* t, uint64_t n, double* x, double* jac,
+                     double* x2);
+
 struct AdaptOptions {
   double rtol = 1e-10, atol = 0.0;
   uint64_t panels = kAdaptDefaultPanels;
   int max_depth = 60;
   uint64_t max_intervals = 1ull << 22;
+  bool unbounded = false;      // accept infinite ends (the map above)
 };
 struct AdaptResult {
   double value = 0.0, err_est = 0.0, resabs = 0.0;
@@ -434,15 +475,20 @@ struct AdaptResult {
   uint64_t floor = 0, forced = 0, nonfinite = 0;
   bool capped = false;
   double device_ms = 0.0;      // events around the call's rounds
+  std::string range = "finite";  // adapt_range_name of the call's range
 };
 
-// Throws, naming the numbers, unless a and b are finite, rtol and atol are >= 0 and not both
-// 0, 1 <= max_intervals <= 2^26, 1 <= panels <= max_intervals and 0 <= max_depth <= 200. No
-// device needed; nothing is launched after a refusal.
+// Throws, naming the numbers, unless a and b are finite (with opt.unbounded: not NaN, and
+// b - a finite when both are), rtol and atol are >= 0 and not both 0, 1 <= max_intervals <=
+// 2^26, 1 <= panels <= max_intervals and 0 <= max_depth <= 200. No device needed; nothing is
+// launched after a refusal.
 void adapt_check(double a, double b, const AdaptOptions& opt);
 std::string expr_adapt_source(const std::string& expr);
 // hipRTC compile for gfx950 (no device needed), cached per expression.
 std::string expr_adapt_compile(const std::string& expr);
+// The eval kernels of the three infinite kinds (the rest of a round is expr_adapt_source's).
+std::string expr_adapt_unbounded_source(const std::string& expr);
+std::string expr_adapt_unbounded_compile(const std::string& expr);
 
 class ExprAdaptive {
  public:
@@ -462,7 +508,10 @@ class ExprAdaptive {
 
  private:
   void reserve(uint64_t max_intervals);
-  AdaptResult rounds(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t cap);
+  // kind kFinite: f on [lo, hi]; else g of that kind and `end` on [lo, hi] = [0, 1].
+  AdaptResult rounds(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t cap,
+                     AdaptRange kind = AdaptRange::kFinite, double end = 0.0);
+  void load_unbounded();
   std::string expr_;
   int device_;
   Stream stream_;
@@ -476,7 +525,8 @@ class ExprAdaptive {
   DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive.cpp)
   PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
   Event e0_, e1_;
-  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+  detail::RtcModule module_;  // the last members: destroyed first (miint/expr_rtc.hpp)
+  std::unique_ptr<detail::RtcModule> unbounded_;  // loaded at the first unbounded call
 };
 
 // ---------------------------------------------------------------------------------------
@@ -524,6 +574,8 @@ class ExprAdaptive {
 // rows * max_intervals <= max_total (the capacity of the two lists) is checked up front and a
 // row's next list never passes its cap, so the lists cannot overflow. a > b integrates [b, a]
 // and negates every value; a == b gives K zero rows with no launch; rows == 0 an empty result.
+// With AdaptSweepOptions::unbounded the shared range may be infinite: the rows run on t in
+// [0, 1] over the mapped integrand (AdaptRange above), the eval kernel replaced by its twin.
 // Left out: the final partition, per-row ranges, multi-rank runs.
 // ---------------------------------------------------------------------------------------
 constexpr uint64_t kAdaptSweepMaxTotalLimit = 1ull << 26;
@@ -536,8 +588,10 @@ struct AdaptSweepOptions {
   int max_depth = 60;
   uint64_t max_intervals = 0;  // per row; 0: max_total / rows
   uint64_t max_total = 1ull << 22;
+  bool unbounded = false;      // accept infinite ends of the shared range (see AdaptOptions)
 };
 struct AdaptSweepResult {
+  std::string range = "finite";  // adapt_range_name of the call's shared range
   // per row
   std::vector<double> value, err_est, resabs, tol;
   std::vector<uint8_t> converged, capped;
@@ -562,6 +616,9 @@ AdaptSweepOptions adapt_sweep_check(uint64_t rows, int nparams, uint64_t param_c
 std::string expr_adapt_sweep_source(const std::string& expr, int nparams);
 // hipRTC compile for gfx950 (no device needed), cached per (expression, nparams).
 std::string expr_adapt_sweep_compile(const std::string& expr, int nparams);
+// The eval kernels of the three infinite kinds (the rest of a round is expr_adapt_sweep_source's).
+std::string expr_adapt_sweep_unbounded_source(const std::string& expr, int nparams);
+std::string expr_adapt_sweep_unbounded_compile(const std::string& expr, int nparams);
 
 class ExprAdaptiveSweep {
  public:
@@ -586,7 +643,9 @@ class ExprAdaptiveSweep {
   };
   void reserve(uint64_t max_total, uint64_t rows);
   void upload(const std::vector<double>& params);
-  Call rounds(double lo, double hi, uint64_t rows, const AdaptSweepOptions& opt);
+  Call rounds(double lo, double hi, uint64_t rows, const AdaptSweepOptions& opt,
+              AdaptRange kind = AdaptRange::kFinite, double end = 0.0);
+  void load_unbounded();
   std::string expr_;
   int nparams_, device_;
   Stream stream_;
@@ -601,7 +660,8 @@ class ExprAdaptiveSweep {
   DeviceBuffer<unsigned long long> state_;   // 16 words per row (expr_adaptive_sweep.cpp)
   PinnedBuffer<unsigned long long> record_;  // the next total and active count
   Event e0_, e1_;
-  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+  detail::RtcModule module_;  // the last members: destroyed first (miint/expr_rtc.hpp)
+  std::unique_ptr<detail::RtcModule> unbounded_;  // loaded at the first unbounded call
 };
 
 // ---------------------------------------------------------------------------------------

@@ -29,6 +29,11 @@ extern const char* const kRtcPrelude;
 // ExprAdaptiveSweep evaluate the same fifteen nodes in the same order.
 std::string adapt_rule_source(const std::string& expr, const std::string& sig,
                               const std::string& args);
+// The same text for an infinite range (miint/expr.hpp, AdaptRange): `expr` becomes
+// miint_user_f(x<sig>), miint_f the map's g(t) around it, and miint_gk15 takes the kind (1 upper,
+// 2 lower, 3 both) and the finite end after hi: miint_gk15(lo, hi, kind, end<args>, &k, &err, &r).
+std::string adapt_unbounded_rule_source(const std::string& expr, const std::string& sig,
+                                        const std::string& args);
 
 // A loaded code object and its kernels. The destructor selects the device, drains the owning
 // object's stream and unloads: declare it as the owner's LAST member, after the Stream, the

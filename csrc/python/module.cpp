@@ -1025,17 +1025,20 @@ PYBIND11_MODULE(_miint, m) {
         "the adaptive kernels evaluate f at");
   py::class_<AdaptOptions>(m, "AdaptOptions", "tolerances and bounds of an adaptive integration")
       .def(py::init([](double rtol, double atol, uint64_t panels, int max_depth,
-                       uint64_t max_intervals) {
+                       uint64_t max_intervals, bool unbounded) {
              AdaptOptions o;
              o.rtol = rtol;
              o.atol = atol;
              o.panels = panels;
              o.max_depth = max_depth;
              o.max_intervals = max_intervals;
+             o.unbounded = unbounded;
              return o;
            }),
            py::arg("rtol") = 1e-10, py::arg("atol") = 0.0, py::arg("panels") = kAdaptDefaultPanels,
-           py::arg("max_depth") = 60, py::arg("max_intervals") = uint64_t(1) << 22)
+           py::arg("max_depth") = 60, py::arg("max_intervals") = uint64_t(1) << 22,
+           py::arg("unbounded") = false)
+      .def_readwrite("unbounded", &AdaptOptions::unbounded)
       .def_readwrite("rtol", &AdaptOptions::rtol)
       .def_readwrite("atol", &AdaptOptions::atol)
       .def_readwrite("panels", &AdaptOptions::panels)
@@ -1056,6 +1059,7 @@ PYBIND11_MODULE(_miint, m) {
       .def_readonly("nonfinite", &AdaptResult::nonfinite)
       .def_readonly("capped", &AdaptResult::capped)
       .def_readonly("device_ms", &AdaptResult::device_ms)
+      .def_readonly("range", &AdaptResult::range)
       .def("as_dict", [](const AdaptResult& r) {
         py::dict d;
         d["value"] = r.value;
@@ -1072,8 +1076,30 @@ PYBIND11_MODULE(_miint, m) {
         d["nonfinite"] = r.nonfinite;
         d["capped"] = r.capped;
         d["device_ms"] = r.device_ms;
+        d["range"] = r.range;
         return d;
       });
+  m.def("adapt_range",
+        [](double a, double b) { return std::string(adapt_range_name(adapt_range(a, b))); },
+        py::arg("a"), py::arg("b"),
+        "'finite', 'upper', 'lower' or 'both': the kind of the range between a and b");
+  m.def("adapt_range_map",
+        [](double a, double b, py::array_t<double, py::array::c_style | py::array::forcecast> t) {
+          MIINT_CHECK(t.ndim() == 1, "adapt_range_map: t is a 1-D array");
+          const py::ssize_t n = t.shape(0);
+          py::array_t<double> x(n), jac(n), x2(n);
+          adapt_range_map(a, b, t.data(), static_cast<uint64_t>(n), x.mutable_data(),
+                          jac.mutable_data(), x2.mutable_data());
+          return py::make_tuple(x, jac, x2);
+        },
+        py::arg("a"), py::arg("b"), py::arg("t"),
+        "the map of an infinite range at every t in (0, 1], in the bits the kernels form: "
+        "(x, jac, x2) with q = (1 - t) / t, jac = t * t and x = a + q (upper), b - q (lower) or "
+        "x = q, x2 = -q (both; x2 = x otherwise): g(t) = f(x) / jac, or (f(x) + f(x2)) / jac");
+  m.def("expr_adapt_unbounded_source", &expr_adapt_unbounded_source, py::arg("expr"),
+        "source of the eval kernels of the infinite kinds for an expression over x");
+  m.def("expr_adapt_unbounded_compile", compiled(&expr_adapt_unbounded_compile), py::arg("expr"),
+        "compile the unbounded eval kernels for gfx950 with hipRTC (no device needed)");
   m.def("adapt_check", &adapt_check, py::arg("a"), py::arg("b"), py::arg("options"),
         "raise, naming the numbers, unless the range and the options are ones ExprAdaptive takes");
   m.def("expr_adapt_source", &expr_adapt_source, py::arg("expr"),
@@ -1102,8 +1128,9 @@ PYBIND11_MODULE(_miint, m) {
   py::class_<AdaptSweepOptions>(m, "AdaptSweepOptions",
                                 "tolerances and bounds of an adaptive sweep (0: derived)")
       .def(py::init([](double rtol, double atol, uint64_t panels, int max_depth,
-                       uint64_t max_intervals, uint64_t max_total) {
+                       uint64_t max_intervals, uint64_t max_total, bool unbounded) {
              AdaptSweepOptions o;
+             o.unbounded = unbounded;
              o.rtol = rtol;
              o.atol = atol;
              o.panels = panels;
@@ -1114,7 +1141,8 @@ PYBIND11_MODULE(_miint, m) {
            }),
            py::arg("rtol") = 1e-10, py::arg("atol") = 0.0, py::arg("panels") = 0,
            py::arg("max_depth") = 60, py::arg("max_intervals") = 0,
-           py::arg("max_total") = uint64_t(1) << 22)
+           py::arg("max_total") = uint64_t(1) << 22, py::arg("unbounded") = false)
+      .def_readwrite("unbounded", &AdaptSweepOptions::unbounded)
       .def_readwrite("rtol", &AdaptSweepOptions::rtol)
       .def_readwrite("atol", &AdaptSweepOptions::atol)
       .def_readwrite("panels", &AdaptSweepOptions::panels)
@@ -1155,8 +1183,15 @@ PYBIND11_MODULE(_miint, m) {
         .def_readonly("call_rounds", &R::call_rounds)
         .def_readonly("call_evals", &R::call_evals)
         .def_readonly("peak", &R::peak)
-        .def_readonly("device_ms", &R::device_ms);
+        .def_readonly("device_ms", &R::device_ms)
+        .def_readonly("range", &R::range);
   }
+  m.def("expr_adapt_sweep_unbounded_source", &expr_adapt_sweep_unbounded_source, py::arg("expr"),
+        py::arg("nparams"),
+        "source of the sweep's eval kernels of the infinite kinds for f(x, p0..p{nparams-1})");
+  m.def("expr_adapt_sweep_unbounded_compile", compiled(&expr_adapt_sweep_unbounded_compile),
+        py::arg("expr"), py::arg("nparams"),
+        "compile the sweep's unbounded eval kernels for gfx950 with hipRTC (no device needed)");
   m.def("adapt_sweep_default_panels", &adapt_sweep_default_panels, py::arg("rows"),
         "the panels a sweep of `rows` rows starts from unless told");
   m.def("adapt_sweep_check", &adapt_sweep_check, py::arg("rows"), py::arg("nparams"),

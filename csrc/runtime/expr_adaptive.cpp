@@ -93,10 +93,60 @@ void gk15_abscissae(double lo, double hi, double* x15) {
   }
 }
 
+const char* adapt_range_name(AdaptRange kind) {
+  switch (kind) {
+    case AdaptRange::kUpper: return "upper";
+    case AdaptRange::kLower: return "lower";
+    case AdaptRange::kBoth: return "both";
+    default: return "finite";
+  }
+}
+
+AdaptRange adapt_range(double a, double b) {
+  if (std::isnan(a) || std::isnan(b) || a == b) return AdaptRange::kFinite;
+  const double lo = std::min(a, b), hi = std::max(a, b);
+  if (std::isinf(lo) && std::isinf(hi)) return AdaptRange::kBoth;
+  if (std::isinf(hi)) return AdaptRange::kUpper;
+  if (std::isinf(lo)) return AdaptRange::kLower;
+  return AdaptRange::kFinite;
+}
+
+void adapt_range_map(double a, double b, const double* t, uint64_t n, double* x, double* jac,
+                     double* x2) {
+#pragma clang fp contract(off)  // the device's three lines, each operation rounded on its own
+  const AdaptRange kind = adapt_range(a, b);
+  MIINT_CHECK(kind != AdaptRange::kBoth || x2 != nullptr,
+              "adapt_range_map: the range (-inf, inf) needs the second abscissa x2");
+  const double end = std::isinf(a) ? b : a;  // the finite one (unused for kBoth)
+  for (uint64_t i = 0; i < n; ++i) {
+    if (kind == AdaptRange::kFinite) {
+      x[i] = t[i];
+      jac[i] = 1.0;
+      if (x2 != nullptr) x2[i] = t[i];
+      continue;
+    }
+    const double q = (1.0 - t[i]) / t[i];
+    jac[i] = t[i] * t[i];
+    if (kind == AdaptRange::kBoth) {
+      x[i] = q;
+      x2[i] = -q;
+    } else {
+      x[i] = kind == AdaptRange::kUpper ? end + q : end - q;
+      if (x2 != nullptr) x2[i] = x[i];
+    }
+  }
+}
+
 void adapt_check(double a, double b, const AdaptOptions& o) {
   const std::string what = "adaptive: ";
-  MIINT_CHECK(std::isfinite(a) && std::isfinite(b) && std::isfinite(b - a),
-              what + "a = " + num(a) + " and b = " + num(b) + " must be finite, and b - a too");
+  if (o.unbounded)
+    MIINT_CHECK(!std::isnan(a) && !std::isnan(b) &&
+                    (std::isinf(a) || std::isinf(b) || std::isfinite(b - a)),
+                what + "a = " + num(a) + " and b = " + num(b) +
+                    " must not be NaN, and b - a must be finite when both are");
+  else
+    MIINT_CHECK(std::isfinite(a) && std::isfinite(b) && std::isfinite(b - a),
+                what + "a = " + num(a) + " and b = " + num(b) + " must be finite, and b - a too");
   MIINT_CHECK(o.rtol >= 0.0 && o.atol >= 0.0 && std::isfinite(o.rtol) && std::isfinite(o.atol) &&
                   (o.rtol > 0.0 || o.atol > 0.0),
               what + "rtol = " + num(o.rtol) + " and atol = " + num(o.atol) +
@@ -148,7 +198,61 @@ __device__ __forceinline__ void miint_gk15(double lo, double hi)" + sig + R"(, d
 }
 )";
 }
+
+std::string adapt_unbounded_rule_source(const std::string& expr, const std::string& sig,
+                                        const std::string& args) {
+  // the user's f under its own name, compiled as adapt_rule_source compiles it; miint_f becomes
+  // g. MIINT_KIND is a literal at every call, so each kernel keeps one branch.
+  return R"(
+__device__ __forceinline__ double miint_user_f(double x)" + sig + R"() { return ()" + expr + R"(); }
+
+// miint/expr.hpp: q = (1.0 - t) / t, then x, then g, each operation rounded on its own.
+// kind 1: (end, +inf); 2: (-inf, end); 3: (-inf, +inf).
+__device__ __forceinline__ double miint_g(double t, const int kind, double end)" + sig + R"() {
+#pragma clang fp contract(off)
+  const double q = (1.0 - t) / t;
+  if (kind == 3) return (miint_user_f(q)" + args + R"() + miint_user_f(-q)" + args + R"()) / (t * t);
+  const double x = kind == 1 ? end + q : end - q;
+  return miint_user_f(x)" + args + R"() / (t * t);
+}
+)" + adapt_rule_source("miint_g(x, miint_kind, miint_end" + args + ")",
+                       ", const int miint_kind, double miint_end" + sig,
+                       ", miint_kind, miint_end" + args);
+}
 }  // namespace detail
+
+std::string expr_adapt_unbounded_source(const std::string& expr) {
+  detail::expr_check_named(expr);
+  std::string src = std::string(detail::kRtcPrelude) + detail::adapt_unbounded_rule_source(expr, "", "");
+  // miint_adapt_eval's twins: the interval is one of t in [0, 1], the block sums and partials
+  // are the same.
+  const char* names[3] = {"upper", "lower", "both"};
+  for (int kind = 1; kind <= 3; ++kind)
+    src += std::string(R"(
+extern "C" __global__ __launch_bounds__(256) void miint_adapt_eval_)") + names[kind - 1] + R"((
+    unsigned long long n, const double2* __restrict__ list, double end, double* __restrict__ k,
+    double* __restrict__ err, double* __restrict__ r, double* __restrict__ part_k) {
+  __shared__ double red[4];
+  const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  double v = 0.0;
+  if (i < n) {
+    const double2 iv = list[i];
+    double e, a;
+    miint_gk15(iv.x, iv.y, )" + std::to_string(kind) + R"(, end, &v, &e, &a);
+    k[i] = v;
+    err[i] = e;
+    r[i] = a;
+  }
+  MIINT_BLOCK_SUM(v, red);
+  if (threadIdx.x == 0) part_k[blockIdx.x] = MIINT_RED(red);
+}
+)";
+  return src;
+}
+
+std::string expr_adapt_unbounded_compile(const std::string& expr) {
+  return detail::rtc_compile_cached(expr_adapt_unbounded_source(expr), expr);
+}
 
 std::string expr_adapt_source(const std::string& expr) {
   detail::expr_check_named(expr);
@@ -387,6 +491,15 @@ ExprAdaptive::ExprAdaptive(const std::string& expr, int device)
   record_ = PinnedBuffer<unsigned long long>(kStateWords);
 }
 
+// The eval kernels of the infinite kinds: compiled (cached per expression) and loaded once, at
+// the object's first unbounded call.
+void ExprAdaptive::load_unbounded() {
+  if (unbounded_) return;
+  unbounded_.reset(new detail::RtcModule(
+      expr_adapt_unbounded_compile(expr_), device_, stream_,
+      {"miint_adapt_eval_upper", "miint_adapt_eval_lower", "miint_adapt_eval_both"}));
+}
+
 // Every buffer holds max_intervals intervals (or their workgroups): sized once for the
 // largest max_intervals asked so far and kept across calls.
 void ExprAdaptive::reserve(uint64_t m) {
@@ -410,7 +523,7 @@ void ExprAdaptive::reserve(uint64_t m) {
 
 // lo < hi. `out` (or null) takes the partition in acceptance order; integrate() orders it.
 AdaptResult ExprAdaptive::rounds(double lo, double hi, const AdaptOptions& opt, double* out,
-                                 uint64_t cap) {
+                                 uint64_t cap, AdaptRange kind, double end) {
   hipStream_t s = stream_.get();
   const unsigned long long max_iv = opt.max_intervals;
   const unsigned max_depth = static_cast<unsigned>(opt.max_depth);
@@ -433,8 +546,12 @@ AdaptResult ExprAdaptive::rounds(double lo, double hi, const AdaptOptions& opt, 
     const double2* list = reinterpret_cast<const double2*>(list_[cur].get());
     double2* next = reinterpret_cast<double2*>(list_[cur ^ 1].get());
     const unsigned* depth = depth_[cur].get();
-    module_.launch(kEval, blocks, 1, kAdaptBlock, s, n, list, k_.get(), err_.get(), r_.get(),
-                   part_k_.get());
+    if (kind == AdaptRange::kFinite)
+      module_.launch(kEval, blocks, 1, kAdaptBlock, s, n, list, k_.get(), err_.get(), r_.get(),
+                     part_k_.get());
+    else  // the twin of the kind: kernels 0, 1, 2 of unbounded_
+      unbounded_->launch(static_cast<size_t>(kind) - 1, blocks, 1, kAdaptBlock, s, n, list, end,
+                         k_.get(), err_.get(), r_.get(), part_k_.get());
     module_.launch(kClose, 1, 1, kAdaptBlock, s, static_cast<const double*>(part_k_.get()), nb,
                    opt.rtol, opt.atol, st);
     module_.launch(kDecide, blocks, 1, kAdaptBlock, s, n, list,
@@ -486,11 +603,17 @@ AdaptResult ExprAdaptive::integrate(double a, double b, const AdaptOptions& opt,
   DeviceGuard g(device_);
   reserve(opt.max_intervals);
   const bool swapped = a > b;
+  const AdaptRange kind = adapt_range(a, b);
+  const bool mapped = kind != AdaptRange::kFinite;
+  if (mapped) load_unbounded();
+  const double end = std::isinf(a) ? b : a;  // the finite end of a half-infinite range
   e0_.record(stream_.get());
-  AdaptResult r = rounds(swapped ? b : a, swapped ? a : b, opt, intervals_out, capacity);
+  AdaptResult r = mapped ? rounds(0.0, 1.0, opt, intervals_out, capacity, kind, end)
+                         : rounds(swapped ? b : a, swapped ? a : b, opt, intervals_out, capacity);
   e1_.record(stream_.get());
   stream_.sync();
   r.device_ms = Event::elapsed_ms(e0_, e1_);
+  r.range = adapt_range_name(kind);
   if (swapped) r.value = -r.value;
   if (intervals_out != nullptr) {
     // the rounds stored the partition in acceptance order: the intervals are disjoint, so the
@@ -500,7 +623,7 @@ AdaptResult ExprAdaptive::integrate(double a, double b, const AdaptOptions& opt,
     MIINT_HIP(hipMemcpy(iv.data(), intervals_out, iv.size() * 2 * sizeof(double),
                         hipMemcpyDeviceToHost));
     std::sort(iv.begin(), iv.end());
-    if (swapped) {  // from a down to b
+    if (swapped && !mapped) {  // from a down to b; a mapped range stays ascending in t
       std::reverse(iv.begin(), iv.end());
       for (auto& p : iv) std::swap(p.first, p.second);
     }
@@ -516,6 +639,13 @@ double ExprAdaptive::time(double a, double b, const AdaptOptions& opt, int iters
   if (a == b) return 0.0;
   DeviceGuard g(device_);
   reserve(opt.max_intervals);
+  const AdaptRange kind = adapt_range(a, b);
+  if (kind != AdaptRange::kFinite) {
+    load_unbounded();
+    const double end = std::isinf(a) ? b : a;
+    return detail::time_enqueues(stream_, e0_, e1_, iters,
+                                 [&] { (void)rounds(0.0, 1.0, opt, nullptr, 0, kind, end); });
+  }
   const double lo = std::min(a, b), hi = std::max(a, b);
   return detail::time_enqueues(stream_, e0_, e1_, iters,
                                [&] { (void)rounds(lo, hi, opt, nullptr, 0); });

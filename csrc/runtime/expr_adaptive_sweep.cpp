@@ -73,6 +73,7 @@ AdaptSweepOptions adapt_sweep_check(uint64_t rows, int nparams, uint64_t param_c
   one.panels = o.panels;
   one.max_depth = o.max_depth;
   one.max_intervals = o.max_intervals;
+  one.unbounded = o.unbounded;
   adapt_check(a, b, one);
   return o;
 }
@@ -299,6 +300,46 @@ extern "C" __global__ __launch_bounds__(256) void miint_asweep_scatter(
 )";
 }
 
+std::string expr_adapt_sweep_unbounded_source(const std::string& expr, int nparams) {
+  detail::expr_check_named(expr);
+  checked_nparams(nparams);
+  std::string sig, load, args;  // as in expr_adapt_sweep_source
+  for (int j = 0; j < nparams; ++j) {
+    const std::string p = "p" + std::to_string(j);
+    sig += ", double " + p;
+    load += "  const double " + p + " = pr[" + std::to_string(j) + "];\n";
+    args += ", " + p;
+  }
+  std::string src = std::string(detail::kRtcPrelude) +
+                    detail::adapt_unbounded_rule_source(expr, sig, args) +
+                    "\n#define MIINT_NPARAMS " + std::to_string(nparams) + "u\n";
+  // miint_asweep_eval's twins: the interval is one of t in [0, 1] (miint/expr.hpp has the map).
+  const char* names[3] = {"upper", "lower", "both"};
+  for (int kind = 1; kind <= 3; ++kind)
+    src += std::string(R"(
+extern "C" __global__ __launch_bounds__(256) void miint_asweep_eval_)") + names[kind - 1] + R"((
+    unsigned n, const double2* __restrict__ list, const unsigned* __restrict__ row,
+    const double* __restrict__ params, double end, double* __restrict__ k,
+    double* __restrict__ err, double* __restrict__ r) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const double2 iv = list[i];
+  const double* __restrict__ pr = params + (unsigned long long)row[i] * MIINT_NPARAMS;
+  (void)pr;
+)" + load + R"(  double v, e, s;
+  miint_gk15(iv.x, iv.y, )" + std::to_string(kind) + ", end" + args + R"(, &v, &e, &s);
+  k[i] = v;
+  err[i] = e;
+  r[i] = s;
+}
+)";
+  return src;
+}
+
+std::string expr_adapt_sweep_unbounded_compile(const std::string& expr, int nparams) {
+  return detail::rtc_compile_cached(expr_adapt_sweep_unbounded_source(expr, nparams), expr);
+}
+
 std::string expr_adapt_sweep_compile(const std::string& expr, int nparams) {
   return detail::rtc_compile_cached(expr_adapt_sweep_source(expr, nparams), expr);
 }
@@ -311,6 +352,15 @@ ExprAdaptiveSweep::ExprAdaptiveSweep(const std::string& expr, int nparams, int d
                "miint_asweep_prefix", "miint_asweep_scatter"}) {
   DeviceGuard g(device);
   record_ = PinnedBuffer<unsigned long long>(kRecordWords);
+}
+
+// The eval kernels of the infinite kinds: compiled (cached per expression and nparams) and
+// loaded once, at the object's first unbounded call.
+void ExprAdaptiveSweep::load_unbounded() {
+  if (unbounded_) return;
+  unbounded_.reset(new detail::RtcModule(
+      expr_adapt_sweep_unbounded_compile(expr_, nparams_), device_, stream_,
+      {"miint_asweep_eval_upper", "miint_asweep_eval_lower", "miint_asweep_eval_both"}));
 }
 
 // The per-interval buffers hold max_total intervals, the per-row ones `rows` rows: sized for
@@ -350,7 +400,8 @@ void ExprAdaptiveSweep::upload(const std::vector<double>& params) {
 
 // lo < hi, opt resolved by adapt_sweep_check.
 ExprAdaptiveSweep::Call ExprAdaptiveSweep::rounds(double lo, double hi, uint64_t rows,
-                                                  const AdaptSweepOptions& opt) {
+                                                  const AdaptSweepOptions& opt, AdaptRange kind,
+                                                  double end) {
   hipStream_t s = stream_.get();
   const unsigned long long max_iv = opt.max_intervals, cap = reserved_;
   const unsigned max_depth = static_cast<unsigned>(opt.max_depth);
@@ -378,8 +429,13 @@ ExprAdaptiveSweep::Call ExprAdaptiveSweep::rounds(double lo, double hi, uint64_t
     const unsigned* depth = depth_[cur].get();
     const unsigned* row = row_[cur].get();
     const unsigned* active = active_[cur].get();
-    module_.launch(kEval, blocks, 1, kBlock, s, n32, list, row,
-                   static_cast<const double*>(params_.get()), k_.get(), err_.get(), r_.get());
+    if (kind == AdaptRange::kFinite)
+      module_.launch(kEval, blocks, 1, kBlock, s, n32, list, row,
+                     static_cast<const double*>(params_.get()), k_.get(), err_.get(), r_.get());
+    else  // the twin of the kind: kernels 0, 1, 2 of unbounded_
+      unbounded_->launch(static_cast<size_t>(kind) - 1, blocks, 1, kBlock, s, n32, list, row,
+                         static_cast<const double*>(params_.get()), end, k_.get(), err_.get(),
+                         r_.get());
     module_.launch(kRow, (na32 + kWavesPerBlock - 1) / kWavesPerBlock, 1, kBlock, s, na32, active,
                    static_cast<const unsigned*>(seg_start_.get()),
                    static_cast<const unsigned*>(seg_len_.get()), list,
@@ -428,8 +484,14 @@ AdaptSweepResult ExprAdaptiveSweep::integrate(const std::vector<double>& params,
   reserve(o.max_total, rows);
   upload(params);
   const bool swapped = a > b;
+  const AdaptRange kind = adapt_range(a, b);
+  const bool mapped = kind != AdaptRange::kFinite;
+  if (mapped) load_unbounded();
+  const double end = std::isinf(a) ? b : a;  // the finite end of a half-infinite range
+  r.range = adapt_range_name(kind);
   e0_.record(stream_.get());
-  const Call c = rounds(swapped ? b : a, swapped ? a : b, rows, o);
+  const Call c = mapped ? rounds(0.0, 1.0, rows, o, kind, end)
+                        : rounds(swapped ? b : a, swapped ? a : b, rows, o);
   e1_.record(stream_.get());
   stream_.sync();
   r.device_ms = Event::elapsed_ms(e0_, e1_);
@@ -467,6 +529,13 @@ double ExprAdaptiveSweep::time(const std::vector<double>& params, uint64_t rows,
   DeviceGuard g(device_);
   reserve(o.max_total, rows);
   upload(params);
+  const AdaptRange kind = adapt_range(a, b);
+  if (kind != AdaptRange::kFinite) {
+    load_unbounded();
+    const double end = std::isinf(a) ? b : a;
+    return detail::time_enqueues(stream_, e0_, e1_, iters,
+                                 [&] { (void)rounds(0.0, 1.0, rows, o, kind, end); });
+  }
   const double lo = std::min(a, b), hi = std::max(a, b);
   return detail::time_enqueues(stream_, e0_, e1_, iters, [&] { (void)rounds(lo, hi, rows, o); });
 }

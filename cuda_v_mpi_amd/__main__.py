@@ -185,9 +185,44 @@ def cmd_compare(a) -> int:
     return 0
 
 
+_INFINITIES = ("inf", "+inf", "-inf", "infinity", "+infinity", "-infinity")
+
+
+def _join_infinities(argv: list) -> list:
+    """``--a -inf`` as ``--a=-inf``: argparse takes a value that starts with a dash and is no
+    plain number for an option of its own."""
+    out, i = [], 0
+    while i < len(argv):
+        if (argv[i] in ("--a", "--b") and i + 1 < len(argv)
+                and argv[i + 1].lower() in _INFINITIES):
+            out.append(f"{argv[i]}={argv[i + 1]}")
+            i += 2
+        else:
+            out.append(argv[i])
+            i += 1
+    return out
+
+
+def _json_ends(rec: dict) -> dict:
+    """An infinite a or b as the string "inf" / "-inf": json has no number for it."""
+    import math
+
+    for k in ("a", "b"):
+        if isinstance(rec.get(k), float) and math.isinf(rec[k]):
+            rec[k] = "inf" if rec[k] > 0 else "-inf"
+    return rec
+
+
 def cmd_integrate(a) -> int:
     from . import Integrator
 
+    for flag, v in (("--a", a.a), ("--b", a.b)):
+        if (v is not None and v in (float("inf"), float("-inf"))
+                and not (a.expr and not a.box and any(t is not None for t in (
+                    a.rtol, a.atol, a.row_rtol, a.row_atol)))):
+            raise SystemExit(f"integrate: {flag} {v}: an infinite range needs --expr with --rtol / "
+                             "--atol or --row-rtol / --row-atol (the fixed rules and --box have no "
+                             "such range)")
     if a.expr:  # any f(x): compiled at run time with hipRTC (ops.kernels.riemann_expr)
         from .ops import kernels
 
@@ -372,7 +407,7 @@ def _integrate_adaptive(a, lo: float, hi: float) -> int:
         print(f"integrate: not converged: err_est {r.err_est:.3g} against tol {r.tol:.3g} "
               f"(capped {int(r.capped)}, nonfinite {r.nonfinite}, forced {r.forced})",
               file=sys.stderr)
-    rec = r.as_dict()
+    rec = _json_ends(r.as_dict())
     rec["value_bits"] = "%016x" % int.from_bytes(__import__("struct").pack("<d", r.value),
                                                  "little")
     if a.analytic is not None:
@@ -430,7 +465,8 @@ def _integrate_adaptive_sweep(a, lo: float, hi: float) -> int:
             print(k, " ".join(f"{p:.17g}" for p in row), f"{v:.17g}")
         return 0
     pack = __import__("struct").pack
-    rec = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.as_dict().items()}
+    rec = _json_ends({k: (v.tolist() if hasattr(v, "tolist") else v)
+                      for k, v in r.as_dict().items()})
     rec["rows"] = len(r.value)
     rec["not_converged"] = missed
     rec["value_bits"] = ["%016x" % int.from_bytes(pack("<d", float(v)), "little")
@@ -541,8 +577,15 @@ def main(argv=None) -> int:
     ig = sub.add_parser("integrate")
     common(ig, integrand="pi4")
     ig.add_argument("--expr", default="", help="any f(x) as one C++ expression over x (hipRTC)")
-    ig.add_argument("--a", type=float, default=None)
-    ig.add_argument("--b", type=float, default=None)
+    ig.add_argument("--a", type=float, default=None, help="the lower end; with --rtol / --atol "
+                    "or --row-rtol / --row-atol also inf, +inf, -inf or infinity (any case): "
+                    "(A, inf), (-inf, B) and (-inf, inf) are mapped onto t in (0, 1] and the "
+                    "rounds bisect t (the record's range: finite, upper, lower or both; resabs is "
+                    "then that of the mapped integrand, for (-inf, inf) the integral of "
+                    "|f(x) + f(-x)| over (0, inf)). A singularity at the finite end ends as "
+                    "nonfinite: split the range there. An oscillatory tail does not converge, "
+                    "and the run says so. Refused without a tolerance flag")
+    ig.add_argument("--b", type=float, default=None, help="the upper end, as --a")
     ig.add_argument("--analytic", type=float, default=None)
     ig.add_argument("--params", default="", help="--expr over x and p0..p7: a file of "
                     "parameter rows (one per line), all rows in one launch")
@@ -601,7 +644,7 @@ def main(argv=None) -> int:
     sc.add_argument("--no-comm", action="store_true")
     sc.add_argument("--jsonl", default="")
     sc.add_argument("--md", default="")
-    a = p.parse_args(argv)
+    a = p.parse_args(_join_infinities(sys.argv[1:] if argv is None else list(argv)))
     if a.cmd == "scale":
         from .parallel import scaling
 

@@ -555,13 +555,14 @@ class AdaptiveResult:
     a: float
     b: float
     backend: str
+    range: str = "finite"   # "upper" (a, inf), "lower" (-inf, b), "both" (-inf, inf)
 
     def as_dict(self) -> dict:
         return dataclasses.asdict(self)
 
 
 _ADAPT_FIELDS = ("value", "err_est", "resabs", "tol", "converged", "evals", "rounds",
-                 "intervals", "splits", "floor", "forced", "nonfinite", "capped")
+                 "intervals", "splits", "floor", "forced", "nonfinite", "capped", "range")
 
 
 def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
@@ -574,13 +575,17 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
     ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr``), one GPU.
     ``backend="cpu"``: the numpy model of the same rule (``utils.adaptive_quad``) on
     ``expr_torch``'s evaluation of the expression (its subset of expressions); needs no GPU.
-    One rank, one f(x), a finite range."""
+    One rank, one f(x). a and b may be infinite (``float("inf")``): (a, inf), (-inf, b) and
+    (-inf, inf) are mapped onto t in (0, 1] and the rounds bisect t; ``range`` names the kind, and
+    err_est, resabs and tol are those of the mapped integrand (for (-inf, inf) resabs is the
+    integral of |f(x) + f(-x)| over (0, inf)). A singularity at the finite end ends as
+    ``nonfinite`` (split the range there), an oscillatory tail does not converge."""
     a, b = float(a), float(b)
     if backend == "hip":
         from .ops import kernels
 
         r = kernels.quad_expr(expr, a, b, rtol=rtol, atol=atol, panels=panels,
-                              max_depth=max_depth, max_intervals=max_intervals)
+                              max_depth=max_depth, max_intervals=max_intervals, unbounded=True)
         fields = {k: getattr(r, k) for k in _ADAPT_FIELDS}
         ms = r.device_ms
     elif backend == "cpu":
@@ -591,7 +596,8 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
 
         t0 = time.perf_counter()
         r = adaptive_model(f, a, b, rtol=rtol, atol=atol, panels=int(panels),
-                           max_depth=int(max_depth), max_intervals=int(max_intervals))
+                           max_depth=int(max_depth), max_intervals=int(max_intervals),
+                           unbounded=True)
         ms = (time.perf_counter() - t0) * 1e3
         fields = {k: r[k] for k in _ADAPT_FIELDS}
     else:
@@ -623,12 +629,13 @@ class AdaptiveSweepResult:
     a: float
     b: float
     backend: str
+    range: str = "finite"      # of the shared range, as in ``AdaptiveResult``
 
     def as_dict(self) -> dict:
         return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
 
 
-_ADAPT_SWEEP_CALL_FIELDS = ("call_rounds", "call_evals", "peak")
+_ADAPT_SWEEP_CALL_FIELDS = ("call_rounds", "call_evals", "peak", "range")
 
 
 def integrate_expr_adaptive_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
@@ -642,13 +649,13 @@ def integrate_expr_adaptive_sweep(expr: str, params, a: float, b: float, rtol: f
     are per row (0: derived), ``max_total`` bounds all rows' intervals together.
     ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr_sweep``),
     one GPU. ``backend="cpu"``: the numpy model (``utils.adaptive_quad.adaptive_sweep_model``)
-    on ``expr_torch``'s subset of expressions; needs no GPU. One rank, one shared finite
-    range."""
+    on ``expr_torch``'s subset of expressions; needs no GPU. One rank, one shared range, whose
+    ends may be infinite as for ``integrate_expr_adaptive``."""
     from .utils.adaptive_quad import SWEEP_ROW_FIELDS, adaptive_sweep_model
 
     a, b = float(a), float(b)
     opts = dict(rtol=rtol, atol=atol, panels=int(panels), max_depth=int(max_depth),
-                max_intervals=int(max_intervals), max_total=int(max_total))
+                max_intervals=int(max_intervals), max_total=int(max_total), unbounded=True)
     if backend == "hip":
         from .ops import kernels
 

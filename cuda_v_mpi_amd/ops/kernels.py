@@ -487,18 +487,22 @@ _EXPR_ADAPT_CACHE: dict = {}
 
 def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
               panels: int = 65536, max_depth: int = 60, max_intervals: int = 1 << 22,
-              return_intervals: bool = False):
+              return_intervals: bool = False, unbounded: bool = False):
     """The integral of any f(x) given as one C++ expression over ``x`` on [a, b] to the
     tolerance max(atol, rtol * |value|): adaptive Gauss-Kronrod (7, 15) from ``panels`` equal
     intervals, bisected by rounds where the estimate misses its share (at most ``max_depth``
     times, ``max_intervals`` intervals in all), six hipRTC-compiled gfx950 kernels cached with
     their module per (expression, device) (csrc/runtime/expr_adaptive.cpp). Returns the native
     AdaptResult: value, err_est, resabs, tol, converged, evals, rounds, intervals, splits,
-    floor, forced, nonfinite, capped, device_ms. With ``return_intervals`` also the final
-    partition as two fp64 device tensors ``lo`` and ``hi``, running from a to b."""
+    floor, forced, nonfinite, capped, device_ms, range. With ``return_intervals`` also the final
+    partition as two fp64 device tensors ``lo`` and ``hi``, running from a to b. With
+    ``unbounded`` a and b may be infinite (refused otherwise): (a, inf), (-inf, b) and
+    (-inf, inf) are mapped onto t in (0, 1] (miint/expr.hpp), the eval kernel's twin for the kind
+    is compiled and loaded at the first such call, ``range`` names the kind, and the partition is
+    that of [0, 1] in t, ascending (``utils.adaptive_quad.t_to_x`` gives the x)."""
     m = native()
     opt = m.AdaptOptions(float(rtol), float(atol), int(panels), int(max_depth),
-                         int(max_intervals))
+                         int(max_intervals), bool(unbounded))
     m.adapt_check(float(a), float(b), opt)  # before any device call
     dev = _device()
     key = (expr, dev.index)
@@ -519,7 +523,7 @@ _EXPR_ADAPT_SWEEP_CACHE: dict = {}
 
 def quad_expr_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
                     atol: float = 0.0, panels: int = 0, max_depth: int = 60,
-                    max_intervals: int = 0, max_total: int = 1 << 22):
+                    max_intervals: int = 0, max_total: int = 1 << 22, unbounded: bool = False):
     """The integrals of f(x, p0, ..., p{nparams-1}) on [a, b] for K parameter rows, each row to
     its own tolerance max(atol, rtol * |value of that row|), in shared rounds: ``params`` is
     K x nparams as for ``riemann_expr_sweep``. Row by row the rule is ``quad_expr``'s, and a
@@ -531,12 +535,13 @@ def quad_expr_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
     arrays value, err_est, resabs, tol, converged, evals, rounds, intervals, splits, floor,
     forced, nonfinite, capped; for the call call_rounds, call_evals, peak, device_ms) and the
     first three of its per-row arrays as 1-D device tensors (fp64, fp64, bool). No rows: empty
-    results, nothing compiled or launched."""
+    results, nothing compiled or launched. With ``unbounded`` the shared a and b may be infinite,
+    as for ``quad_expr``; the result's ``range`` names the kind."""
     m = native()
     p = _param_rows(params)
     rows, nparams = p.shape
     opt = m.AdaptSweepOptions(float(rtol), float(atol), int(panels), int(max_depth),
-                              int(max_intervals), int(max_total))
+                              int(max_intervals), int(max_total), bool(unbounded))
     m.adapt_sweep_check(int(rows), int(nparams), int(p.size), float(a), float(b), opt)
     dev = _device()
     if rows == 0:

@@ -10,6 +10,14 @@ not bit for bit, and a decision on the border of a bound may fall the other way.
 
     r = adaptive_model(lambda x: 1.0 / (x * x + 1e-8), -1.0, 1.0, rtol=1e-10)
     r["value"], r["err_est"], r["converged"], r["lo"], r["hi"]
+
+Infinite ranges (``unbounded=True``; miint/expr.hpp has the rule): the rounds run on t in
+[0, 1] over g(t) = f(x(t)) / (t * t), with x and the divisor taken from the native
+``adapt_range_map``, so f is evaluated at the device's bits. ``lo`` and ``hi`` are then the
+partition in t, ascending; ``t_to_x`` gives the x.
+
+    r = adaptive_model(lambda x: np.exp(-x * x), -np.inf, np.inf, unbounded=True)
+    r["range"], t_to_x(-np.inf, np.inf, r["lo"])
 """
 from __future__ import annotations
 
@@ -20,9 +28,15 @@ DEFAULTS = dict(rtol=1e-10, atol=0.0, panels=65536, max_depth=60, max_intervals=
 
 
 def check_options(a: float, b: float, rtol: float, atol: float, panels: int, max_depth: int,
-                  max_intervals: int) -> None:
+                  max_intervals: int, unbounded: bool = False) -> None:
     """The refusals of ``adapt_check``, with the numbers named."""
-    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(b - a)):
+    with np.errstate(invalid="ignore", over="ignore"):
+        width_ok = bool(np.isfinite(np.float64(b) - np.float64(a)))
+    if unbounded:
+        if np.isnan(a) or np.isnan(b) or not (np.isinf(a) or np.isinf(b) or width_ok):
+            raise ValueError(f"adaptive: a = {a:.17g} and b = {b:.17g} must not be NaN, and "
+                             "b - a must be finite when both are")
+    elif not (np.isfinite(a) and np.isfinite(b) and width_ok):
         raise ValueError(f"adaptive: a = {a:.17g} and b = {b:.17g} must be finite, and b - a too")
     if not (rtol >= 0 and atol >= 0 and np.isfinite(rtol) and np.isfinite(atol)
             and (rtol > 0 or atol > 0)):
@@ -61,18 +75,69 @@ def gk15(f, lo: np.ndarray, hi: np.ndarray):
     return k, np.abs(k - g), hw * sa
 
 
+def range_kind(a: float, b: float) -> str:
+    """'finite', 'upper', 'lower' or 'both': ``adapt_range`` (a == b and NaN ends: 'finite')."""
+    a, b = float(a), float(b)
+    if np.isnan(a) or np.isnan(b) or a == b:
+        return "finite"
+    lo, hi = min(a, b), max(a, b)
+    if np.isinf(lo) and np.isinf(hi):
+        return "both"
+    return "upper" if np.isinf(hi) else "lower" if np.isinf(lo) else "finite"
+
+
+def t_to_x(a: float, b: float, t):
+    """The x of every t of an unbounded run's partition, in the kernels' bits: a + (1 - t) / t
+    for (a, inf), b - (1 - t) / t for (-inf, b), and for (-inf, inf) the positive one q =
+    (1 - t) / t of the two abscissae q and -q. t = 0 is the infinite end. A finite range
+    returns t."""
+    from .._native import native
+
+    t = np.asarray(t, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        x = native().adapt_range_map(float(a), float(b), t.ravel())[0]
+    return x.reshape(t.shape)
+
+
+def mapped_integrand(f, a: float, b: float):
+    """g of miint/expr.hpp for the infinite range between a and b: g(t) = f(x) / (t * t), or
+    (f(q) + f(-q)) / (t * t), with x, q and t * t from the native ``adapt_range_map``."""
+    from .._native import native
+
+    m = native()
+    kind = range_kind(a, b)
+    assert kind != "finite"
+
+    def g(t):
+        x, jac, x2 = (v.reshape(t.shape) for v in m.adapt_range_map(a, b, t.ravel()))
+        if kind == "both":
+            return (np.asarray(f(x), dtype=np.float64) + np.asarray(f(x2), dtype=np.float64)) / jac
+        return np.asarray(f(x), dtype=np.float64) / jac
+
+    return g
+
+
 def adaptive_model(f, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
                    panels: int = 65536, max_depth: int = 60,
-                   max_intervals: int = 1 << 22) -> dict:
+                   max_intervals: int = 1 << 22, unbounded: bool = False) -> dict:
     """The integral of f on [a, b] by the rounds of ExprAdaptive. ``f`` maps an fp64 array to
     an fp64 array. Returns the fields of AdaptResult (``device_ms`` aside), ``peak`` (the
-    longest active list) and the final partition ``lo``, ``hi`` running from a to b."""
+    longest active list) and the final partition ``lo``, ``hi`` running from a to b (for an
+    infinite range, with ``unbounded``: the partition of [0, 1] in t, ascending)."""
     a, b = float(a), float(b)
-    check_options(a, b, rtol, atol, panels, max_depth, max_intervals)
+    check_options(a, b, rtol, atol, panels, max_depth, max_intervals, unbounded)
     out = dict(value=0.0, err_est=0.0, resabs=0.0, tol=float(atol), converged=True, evals=0,
                rounds=0, intervals=0, splits=0, floor=0, forced=0, nonfinite=0, capped=False,
-               peak=0, lo=np.empty(0), hi=np.empty(0))
+               peak=0, lo=np.empty(0), hi=np.empty(0), range="finite")
     if a == b:
+        return out
+    kind = range_kind(a, b)
+    if kind != "finite":  # the same rounds on g over [0, 1], W = 1
+        out = adaptive_model(mapped_integrand(f, a, b), 0.0, 1.0, rtol=rtol, atol=atol,
+                             panels=panels, max_depth=max_depth, max_intervals=max_intervals)
+        out["range"] = kind
+        if a > b:
+            out["value"] = -out["value"]
         return out
     swapped = a > b
     x0, x1 = (b, a) if swapped else (a, b)
@@ -155,7 +220,7 @@ def sweep_default_panels(rows: int) -> int:
 def check_sweep_options(rows: int, nparams: int, param_count: int, a: float, b: float,
                         rtol: float = 1e-10, atol: float = 0.0, panels: int = 0,
                         max_depth: int = 60, max_intervals: int = 0,
-                        max_total: int = 1 << 22) -> dict:
+                        max_total: int = 1 << 22, unbounded: bool = False) -> dict:
     """The refusals of ``adapt_sweep_check``, with its wording; returns ``panels`` and
     ``max_intervals`` with their zeros resolved."""
     what = "adaptive sweep: "
@@ -178,7 +243,7 @@ def check_sweep_options(rows: int, nparams: int, param_count: int, a: float, b: 
     if max_intervals > max_total // k:
         raise ValueError(f"{what}rows * max_intervals = {rows} * {max_intervals} passes "
                          f"max_total = {max_total}")
-    check_options(a, b, rtol, atol, panels, max_depth, max_intervals)
+    check_options(a, b, rtol, atol, panels, max_depth, max_intervals, unbounded)
     return dict(panels=panels, max_intervals=max_intervals)
 
 
@@ -188,13 +253,13 @@ SWEEP_ROW_FIELDS = ("value", "err_est", "resabs", "tol", "converged", "evals", "
 
 def adaptive_sweep_model(f, params, a: float, b: float, rtol: float = 1e-10, atol: float = 0.0,
                          panels: int = 0, max_depth: int = 60, max_intervals: int = 0,
-                         max_total: int = 1 << 22) -> dict:
+                         max_total: int = 1 << 22, unbounded: bool = False) -> dict:
     """The integrals of f(x, *row) on [a, b] for every row of ``params`` (K x nparams) by the
     rounds of ExprAdaptiveSweep. A row's result does not depend on the rows that ride along, so
     this is ``adaptive_model`` row by row on the resolved options. Returns the per-row fields of
     AdaptSweepResult as arrays, ``peak_row`` (each row's longest list), and for the call
     ``call_rounds`` (the maximum), ``call_evals`` (the sum) and ``peak`` (the longest whole
-    list: rows share rounds, so round t holds every row's t-th list)."""
+    list: rows share rounds, so round t holds every row's t-th list), and ``range``."""
     p = np.asarray(params, dtype=np.float64)
     if p.ndim == 1 and p.size == 0:
         p = p.reshape(0, 0)
@@ -203,19 +268,28 @@ def adaptive_sweep_model(f, params, a: float, b: float, rtol: float = 1e-10, ato
     rows, nparams = p.shape
     a, b = float(a), float(b)
     res = check_sweep_options(rows, nparams, p.size, a, b, rtol, atol, panels, max_depth,
-                              max_intervals, max_total)
+                              max_intervals, max_total, unbounded)
+    kind = range_kind(a, b)
     runs = []
     sizes: dict = {}
     for row in p:
         def frow(x, row=row):
             return f(x, *row)
 
-        def counted(x, key=len(runs)):
-            sizes.setdefault(key, []).append(x.shape[0])
-            return frow(x)
+        # an infinite range: the rounds see g on [0, 1], as adaptive_model would run them
+        h = frow if kind == "finite" else mapped_integrand(frow, a, b)
 
-        runs.append(adaptive_model(counted, a, b, rtol=rtol, atol=atol, panels=res["panels"],
-                                   max_depth=max_depth, max_intervals=res["max_intervals"]))
+        def counted(x, key=len(runs), h=h):
+            sizes.setdefault(key, []).append(x.shape[0])
+            return h(x)
+
+        lo, hi = (a, b) if kind == "finite" else (0.0, 1.0)
+        run = adaptive_model(counted, lo, hi, rtol=rtol, atol=atol, panels=res["panels"],
+                             max_depth=max_depth, max_intervals=res["max_intervals"],
+                             unbounded=unbounded)
+        if kind != "finite" and a > b:
+            run["value"] = -run["value"]
+        runs.append(run)
     out = {}
     kinds = dict(converged=bool, capped=bool, value=np.float64, err_est=np.float64,
                  resabs=np.float64, tol=np.float64)
@@ -227,5 +301,6 @@ def adaptive_sweep_model(f, params, a: float, b: float, rtol: float = 1e-10, ato
     out["call_rounds"] = int(out["rounds"].max()) if rows else 0
     out["call_evals"] = int(out["evals"].sum())
     out["peak"] = max(whole, default=0)
+    out["range"] = range_kind(a, b)
     out.update(res)
     return out
