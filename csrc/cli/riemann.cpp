@@ -553,6 +553,92 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
   cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
   return 0;
 }
+
+// --expr with --ya / --yb and --area-rtol / --area-atol: the double integral to a tolerance
+// (ExprAdaptive2D). One GPU, one rank. Refusals come before any device call.
+bool area_adaptive_requested(const cli::Args& a) {
+  return a.has("area-rtol") || a.has("area-atol");
+}
+bool row_adaptive_requested(const cli::Args& a);
+
+int run_expr_adaptive2d(const cli::Args& a, const RiemannConfig& cfg) {
+  const std::string who = "--area-rtol / --area-atol";
+  MIINT_CHECK(a.has("ya") && a.has("yb"),
+              who + " are the tolerance of a double integral: they need --ya AY --yb BY");
+  MIINT_CHECK(!adaptive_requested(a), who + " are the tolerance of a double integral: --rtol / "
+                                            "--atol do not go with them");
+  MIINT_CHECK(!row_adaptive_requested(a), who + " are the tolerance of a double integral: "
+                                                "--row-rtol / --row-atol do not go with them");
+  for (const char* k : {"n", "ny", "rule", "running", "params", "linspace", "every",
+                        "running-out", "loopback", "box"})
+    MIINT_CHECK(!a.has(k), who + " choose the samples themselves: --" + k +
+                               " does not go with them");
+  MIINT_CHECK(a.integer("gpus", 1) <= 1, who + " run on one GPU: --gpus " + a.str("gpus", "") +
+                                             " does not go with them (the tolerance would need a "
+                                             "collective every round)");
+  MIINT_CHECK(cli::env_int("WORLD_SIZE", 1) <= 1,
+              who + " run as one rank: a rank environment (WORLD_SIZE = " +
+                  std::to_string(cli::env_int("WORLD_SIZE", 1)) + ") does not go with them");
+  MIINT_CHECK(!cli::on_cpu(a), who + " have no host engine: --device cpu does not go with them");
+  Adapt2DOptions o;
+  o.rtol = adaptive_number(a, "area-rtol", o.rtol, false);
+  o.atol = adaptive_number(a, "area-atol", 0.0, false);
+  const double px = adaptive_number(a, "panels", static_cast<double>(o.panels_x), true);
+  const double py = adaptive_number(a, "panels-y", px, true);
+  const double depth = adaptive_number(a, "max-depth", o.max_depth, true);
+  const double max_iv =
+      adaptive_number(a, "max-intervals", static_cast<double>(o.max_intervals), true);
+  MIINT_CHECK(px >= 0 && py >= 0 && max_iv >= 0 && std::fabs(depth) < 1e9,
+              "--panels, --panels-y, --max-intervals and --max-depth must not be negative or "
+              "huge");
+  o.panels_x = static_cast<uint64_t>(px);
+  o.panels_y = static_cast<uint64_t>(py);
+  o.max_depth = static_cast<int>(depth);
+  o.max_intervals = static_cast<uint64_t>(max_iv);
+  const double ya = a.num("ya", 0.0), yb = a.num("yb", 0.0);
+  adapt2d_check(cfg.a, cfg.b, ya, yb, o);
+  const std::string expr = a.str("expr", "");
+  (void)expr_adapt2d_source(expr);  // a rejected expression: before any device call
+  MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprAdaptive2D ea(expr, 0);
+  const Adapt2DResult r = ea.integrate(cfg.a, cfg.b, ya, yb, o);
+  const double secs = wall_seconds() - process_start_seconds();
+  if (!r.converged)
+    std::fprintf(stderr, "riemann: not converged: err_est %.3g against tol %.3g (capped %d, "
+                 "nonfinite %llu, forced %llu)\n", r.err_est, r.tol, r.capped ? 1 : 0,
+                 static_cast<unsigned long long>(r.nonfinite),
+                 static_cast<unsigned long long>(r.forced));
+  if (!a.flag("json")) std::printf("%.17g\n", r.value);
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
+      .add("ya", ya).add("yb", yb).add("rtol", o.rtol).add("atol", o.atol)
+      .add("panels", static_cast<double>(o.panels_x))
+      .add("panels_y", static_cast<double>(o.panels_y)).add("max_depth", o.max_depth)
+      .add("max_intervals", static_cast<double>(o.max_intervals))
+      .add("value", r.value).add("err_est", r.err_est).add("resabs", r.resabs).add("tol", r.tol)
+      .add("converged", r.converged).add("evals", static_cast<double>(r.evals))
+      .add("rounds", static_cast<double>(r.rounds))
+      .add("intervals", static_cast<double>(r.intervals))
+      .add("splits", static_cast<double>(r.splits))
+      .add("splits_x", static_cast<double>(r.splits_x))
+      .add("splits_y", static_cast<double>(r.splits_y))
+      .add("floor", static_cast<double>(r.floor)).add("forced", static_cast<double>(r.forced))
+      .add("nonfinite", static_cast<double>(r.nonfinite)).add("capped", r.capped);
+  // %.17g round-trips a finite value; a non-finite one prints as null, its bits are here
+  char bits[24];
+  uint64_t w = 0;
+  std::memcpy(&w, &r.value, sizeof w);
+  std::snprintf(bits, sizeof bits, "%016llx", static_cast<unsigned long long>(w));
+  rec.add("value_bits", bits);
+  if (a.has("analytic")) {
+    const double exact = a.num("analytic", 0.0);
+    rec.add("analytic", exact).add("abs_err", std::fabs(r.value - exact));
+  }
+  cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr with --params / --linspace and --row-rtol / --row-atol: every row to its own tolerance
 // in shared rounds (ExprAdaptiveSweep). One GPU, one rank. Refusals come before any device call.
 bool row_adaptive_requested(const cli::Args& a) { return a.has("row-rtol") || a.has("row-atol"); }
@@ -814,6 +900,7 @@ int run_expr_lattice(const cli::Args& a, int iters) {
 
 // --expr (see the header comment): GPU ranks as in the default path, f compiled by hipRTC.
 int run_expr(const cli::Args& a, const RiemannConfig& cfg, double nd, int iters) {
+  if (area_adaptive_requested(a)) return run_expr_adaptive2d(a, cfg);
   if (row_adaptive_requested(a)) return run_expr_adaptive_sweep(a, cfg);
   if (a.has("box")) return run_expr_lattice(a, iters);
   if (adaptive_requested(a)) return run_expr_adaptive(a, cfg);
@@ -878,6 +965,8 @@ constexpr const char* kUsage =
     "               [--expr EXPR --params FILE | --linspace p0=LO:HI:COUNT]\n"
     "               [--expr EXPR --a A --b B --n N --running [--every K] [--running-out FILE]]\n"
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
+    "               [--expr EXPR --a AX --b BX --ya AY --yb BY --area-rtol R [--area-atol T]\n"
+    "                [--panels P] [--panels-y Q] [--max-depth D] [--max-intervals M]]\n"
     "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
     "                [--max-intervals M]]\n"
     "               [--expr EXPR --a A --b B --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
@@ -894,6 +983,18 @@ constexpr const char* kUsage =
     "  samples (--ny defaults to --n), the same rule on both axes; ranks split the sample rows\n"
     "  (--gpus, --loopback, rank environment, --device cpu [--threads T] as for --expr);\n"
     "  --json: expr, a, b, ya, yb, n, ny, rule, value, device_ms, samples_per_s.\n"
+    "--area-rtol R / --area-atol T: with --ya AY --yb BY, the double integral of --expr over the\n"
+    "  finite rectangle to the tolerance max(T, R |value|): the (7, 15) x (7, 15) Gauss-Kronrod\n"
+    "  product, 225 evaluations a rectangle, from --panels P x --panels-y Q equal rectangles\n"
+    "  (default 64, Q defaults to P), each bisected along the axis with the larger error, at most\n"
+    "  --max-depth D times per axis (default 60), at most --max-intervals M rectangles in all\n"
+    "  (default 2^22). Prints the value, and a warning on stderr when not converged; --json:\n"
+    "  value, err_est, resabs, tol, converged, evals, rounds, intervals, splits, splits_x,\n"
+    "  splits_y, floor, forced, nonfinite, capped, device_ms. One GPU, one rank, no host engine:\n"
+    "  refused without --ya / --yb, with --n, --ny, --rule, --running, --params, --linspace, --box,\n"
+    "  --rtol, --atol, --row-rtol, --row-atol, --gpus above 1, --loopback, WORLD_SIZE above 1 or\n"
+    "  --device cpu, and with an infinite side. A discontinuity along a curve (an indicator) runs\n"
+    "  to the cap and reports capped: use the fixed rule or --box there.\n"
     "--rtol R / --atol T: the integral of --expr on [A, B] to the tolerance max(T, R |value|)\n"
     "  (adaptive Gauss-Kronrod (7, 15) from --panels P equal intervals, default 65536, bisected at\n"
     "  most --max-depth D times, default 60, at most --max-intervals M in all, default 2^22);\n"
@@ -988,7 +1089,11 @@ int main(int argc, char** argv) {
                 "--rtol / --atol are the tolerance of an --expr integrand");
     MIINT_CHECK(a.has("expr") || !row_adaptive_requested(a),
                 "--row-rtol / --row-atol are the per-row tolerance of an --expr parameter sweep");
-    MIINT_CHECK(adaptive_requested(a) || row_adaptive_requested(a) ||
+    MIINT_CHECK(a.has("expr") || !area_adaptive_requested(a),
+                "--area-rtol / --area-atol are the tolerance of an --expr double integral");
+    MIINT_CHECK(area_adaptive_requested(a) || !a.has("panels-y"),
+                "--panels-y belongs to --area-rtol / --area-atol");
+    MIINT_CHECK(adaptive_requested(a) || row_adaptive_requested(a) || area_adaptive_requested(a) ||
                     !(a.has("panels") || a.has("max-depth") || a.has("max-intervals")),
                 "--panels / --max-depth / --max-intervals belong to --rtol / --atol");
     MIINT_CHECK(row_adaptive_requested(a) || !a.has("max-total"),

@@ -530,6 +530,120 @@ class ExprAdaptive {
 };
 
 // ---------------------------------------------------------------------------------------
+// Adaptive double integrals: the integral of f(x, y) over a finite rectangle [ax, bx] x [ay, by]
+// to max(atol, rtol |value|), with an error estimate and a `converged` flag.
+//
+// ExprIntegrator2D sums nx x ny equally spaced samples and leaves both to the caller. Here the
+// tensor product of the (7, 15) pair above is applied to a list of rectangles, and a rectangle
+// whose estimate misses its share (by area) of the tolerance is bisected along the axis that
+// carries more of the error, round by round (expr_adaptive2d.cpp).
+//
+// Per rectangle [x0, x1] x [y0, y1], 225 evaluations, none on an edge:
+//   hx = 0.5 (x1 - x0), cx = x0 + hx, x nodes cx and fma(hx, -+t_i, cx); the same in y.
+//   Row at y node j (the 1-D order: the centre, then the pairs (-t_i, +t_i) outwards, by fma):
+//     rk_j = sum_i wk_i f,  rg_j = sum_{i Gauss} wg_i f,  ra_j = sum_i wk_i |f|
+//     centre: rk = wk_0 f0, rg = wg_0 f0, ra = wk_0 |f0|;
+//     pair i: rk = fma(wk_i, f1 + f2, rk), ra = fma(wk_i, |f1| + |f2|, ra), and for the even
+//     (Gauss) i rg = fma(wg_i, f1 + f2, rg), f1 at -t_i and f2 at +t_i.
+//   The rows are combined in the same order over j: the centre row first, then per pair the
+//   two rows' sums added (the row at -t_j first) and carried by fma:
+//     KK = sum_j wk_j rk_j,  GK = sum_j wk_j rg_j,  RA = sum_j wk_j ra_j   (all j)
+//     GG = sum_j wg_j rg_j,  KG = sum_j wg_j rk_j                          (the even, Gauss j)
+//   With s = hx * hy: K = s KK, err = |s KK - s GG|, ex = |s KK - s GK| (the Gauss rule along x
+//   only: the x direction's error), ey = |s KK - s KG|, R = s RA. Contraction is off where
+//   these are rounded and compared, as in miint_gk15.
+// Split axis: x if ex > ey, y if ey > ex; on a tie x when wx * Wy >= wy * Wx (the relatively
+// wider side), else y; w the rectangle's sides, W the box's.
+// Decision, in this order: K or err not finite -> accept, counted in `nonfinite`;
+// not (err > (tol (wx wy)) / (Wx Wy)) -> accept; err <= 50 * 2^-52 R -> accept, `floor`; the
+// chosen axis's own depth >= max_depth, or its midpoint equal to one of its ends -> accept,
+// `forced`; else bisect along the chosen axis, the children taking slots 2 p and 2 p + 1 of the
+// next list (p: the rectangles split before it). A rectangle carries one depth per axis (the
+// halves of one 32-bit word).
+//
+// The list starts as panels_x x panels_y equal rectangles, x fastest, each axis's edges formed
+// as miint_adapt_init forms them. A round is ExprAdaptive's: miint_adapt2d_eval (one rectangle
+// per lane; the loop over the 15 rows is rolled, a row's 15 evaluations unrolled in it),
+// _close (sum_K and tol = max(atol, rtol |S_acc + sum_K|) on the device), _decide, _prefix
+// (the cap: accepted + (n - splits) + 2 splits > max_intervals splits nothing and the pending
+// sums join the totals; the eighteen-word record: ExprAdaptive's sixteen, then splits_x and
+// splits_y) and _scatter; one sync per round, at most 2 max_depth + 1 rounds, no workgroup
+// waits on another, every sum in an order fixed by the list length: bitwise reproducible.
+// ax > bx negates, ay > by negates; either pair equal gives 0 with no launch. Infinite sides,
+// parameter rows and more than one rank are left out.
+// A limit: a discontinuity along a curve leaves err proportional to the area of the rectangles
+// it cuts, so their share of the tolerance is never met: such a run ends `capped` (an
+// indicator's tool is the fixed rule or the lattice). A point or edge singularity is resolved
+// as far as the doubles go, at up to 61 (one axis) or 121 rounds.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t kAdapt2DDefaultPanels = 64;  // per axis: 4096 rectangles, 921 600 evaluations
+
+struct Adapt2DOptions {
+  double rtol = 1e-10, atol = 0.0;
+  uint64_t panels_x = kAdapt2DDefaultPanels, panels_y = kAdapt2DDefaultPanels;
+  int max_depth = 60;          // per axis
+  uint64_t max_intervals = 1ull << 22;
+};
+struct Adapt2DResult {
+  double value = 0.0, err_est = 0.0, resabs = 0.0;
+  double tol = 0.0;            // the last round's tolerance
+  bool converged = false;      // err_est <= tol, not capped, nonfinite == 0
+  uint64_t evals = 0;          // 225 x rectangles evaluated
+  uint64_t rounds = 0, intervals = 0, splits = 0;
+  uint64_t splits_x = 0, splits_y = 0;  // splits = splits_x + splits_y
+  uint64_t floor = 0, forced = 0, nonfinite = 0;
+  bool capped = false;
+  double device_ms = 0.0;      // events around the call's rounds
+};
+
+// Throws, naming the numbers, unless the four ends, both widths and the area are finite, rtol
+// and atol are >= 0 and not both 0, 1 <= max_intervals <= 2^26, panels_x, panels_y >= 1 with
+// panels_x * panels_y <= max_intervals, and 0 <= max_depth <= 200. No device needed; nothing
+// is launched after a refusal.
+void adapt2d_check(double ax, double bx, double ay, double by, const Adapt2DOptions& opt);
+std::string expr_adapt2d_source(const std::string& expr);
+// hipRTC compile for gfx950 (no device needed), cached per expression.
+std::string expr_adapt2d_compile(const std::string& expr);
+
+class ExprAdaptive2D {
+ public:
+  ExprAdaptive2D(const std::string& expr, int device = 0);
+  ExprAdaptive2D(const ExprAdaptive2D&) = delete;
+  ExprAdaptive2D& operator=(const ExprAdaptive2D&) = delete;
+  // The integral of f over the rectangle by the rounds above. With rects_out (device memory,
+  // `capacity` x 4 doubles; refused up front unless capacity >= max_intervals) the final
+  // partition is also stored there as (x0, x1, y0, y1) with x0 < x1 and y0 < y1, ordered by
+  // (y0, x0): result.intervals of them. Synchronous: one sync per round.
+  Adapt2DResult integrate(double ax, double bx, double ay, double by,
+                          const Adapt2DOptions& opt = {}, double* rects_out = nullptr,
+                          uint64_t capacity = 0);
+  // Device ms per call over `iters` back-to-back calls (events around them; the rounds' syncs
+  // and the host's reads between them are inside).
+  double time(double ax, double bx, double ay, double by, const Adapt2DOptions& opt, int iters);
+  const std::string& expression() const { return expr_; }
+
+ private:
+  void reserve(uint64_t max_intervals);
+  Adapt2DResult rounds(double x0, double x1, double y0, double y1, const Adapt2DOptions& opt,
+                       double* out, uint64_t cap);
+  std::string expr_;
+  int device_;
+  Stream stream_;
+  uint64_t reserved_ = 0;
+  DeviceBuffer<double> xs_[2], ys_[2];  // (x0, x1) and (y0, y1) pairs: 2 x max_intervals each
+  DeviceBuffer<unsigned> depth_[2];     // x depth | y depth << 16
+  DeviceBuffer<double> k_, err_, r_;    // per rectangle
+  DeviceBuffer<double> dir_;            // per rectangle: (ex, ey)
+  DeviceBuffer<unsigned char> split_;   // per rectangle: 0 accepted, 1 bisect x, 2 bisect y
+  DeviceBuffer<double> part_k_, blk_sums_;  // per workgroup: 1 and 5 doubles
+  DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 5 counters; the split prefix
+  DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive2d.cpp)
+  PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
+  Event e0_, e1_;
+  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+};
+
+// ---------------------------------------------------------------------------------------
 // Adaptive sweeps: f(x, p0..p{nparams-1}) on a shared [a, b] for K parameter rows, each row to
 // its own tolerance max(atol, rtol |value of that row|), in shared rounds.
 //

@@ -1121,6 +1121,94 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprAdaptive::expression);
 
+  // adaptive double integrals: the (7, 15) x (7, 15) product on rectangles bisected by rounds
+  m.attr("ADAPT2D_DEFAULT_PANELS") = kAdapt2DDefaultPanels;
+  py::class_<Adapt2DOptions>(m, "Adapt2DOptions",
+                             "tolerances and bounds of an adaptive double integral")
+      .def(py::init([](double rtol, double atol, uint64_t panels_x, uint64_t panels_y,
+                       int max_depth, uint64_t max_intervals) {
+             Adapt2DOptions o;
+             o.rtol = rtol;
+             o.atol = atol;
+             o.panels_x = panels_x;
+             o.panels_y = panels_y;
+             o.max_depth = max_depth;
+             o.max_intervals = max_intervals;
+             return o;
+           }),
+           py::arg("rtol") = 1e-10, py::arg("atol") = 0.0,
+           py::arg("panels_x") = kAdapt2DDefaultPanels,
+           py::arg("panels_y") = kAdapt2DDefaultPanels, py::arg("max_depth") = 60,
+           py::arg("max_intervals") = uint64_t(1) << 22)
+      .def_readwrite("rtol", &Adapt2DOptions::rtol)
+      .def_readwrite("atol", &Adapt2DOptions::atol)
+      .def_readwrite("panels_x", &Adapt2DOptions::panels_x)
+      .def_readwrite("panels_y", &Adapt2DOptions::panels_y)
+      .def_readwrite("max_depth", &Adapt2DOptions::max_depth)
+      .def_readwrite("max_intervals", &Adapt2DOptions::max_intervals);
+  py::class_<Adapt2DResult>(m, "Adapt2DResult", "value, error estimate and counters of one call")
+      .def(py::init<>())
+      .def_readonly("value", &Adapt2DResult::value)
+      .def_readonly("err_est", &Adapt2DResult::err_est)
+      .def_readonly("resabs", &Adapt2DResult::resabs)
+      .def_readonly("tol", &Adapt2DResult::tol)
+      .def_readonly("converged", &Adapt2DResult::converged)
+      .def_readonly("evals", &Adapt2DResult::evals)
+      .def_readonly("rounds", &Adapt2DResult::rounds)
+      .def_readonly("intervals", &Adapt2DResult::intervals)
+      .def_readonly("splits", &Adapt2DResult::splits)
+      .def_readonly("splits_x", &Adapt2DResult::splits_x)
+      .def_readonly("splits_y", &Adapt2DResult::splits_y)
+      .def_readonly("floor", &Adapt2DResult::floor)
+      .def_readonly("forced", &Adapt2DResult::forced)
+      .def_readonly("nonfinite", &Adapt2DResult::nonfinite)
+      .def_readonly("capped", &Adapt2DResult::capped)
+      .def_readonly("device_ms", &Adapt2DResult::device_ms)
+      .def("as_dict", [](const Adapt2DResult& r) {
+        py::dict d;
+        d["value"] = r.value;
+        d["err_est"] = r.err_est;
+        d["resabs"] = r.resabs;
+        d["tol"] = r.tol;
+        d["converged"] = r.converged;
+        d["evals"] = r.evals;
+        d["rounds"] = r.rounds;
+        d["intervals"] = r.intervals;
+        d["splits"] = r.splits;
+        d["splits_x"] = r.splits_x;
+        d["splits_y"] = r.splits_y;
+        d["floor"] = r.floor;
+        d["forced"] = r.forced;
+        d["nonfinite"] = r.nonfinite;
+        d["capped"] = r.capped;
+        d["device_ms"] = r.device_ms;
+        return d;
+      });
+  m.def("adapt2d_check", &adapt2d_check, py::arg("ax"), py::arg("bx"), py::arg("ay"),
+        py::arg("by"), py::arg("options"),
+        "raise, naming the numbers, unless the rectangle and the options are ones ExprAdaptive2D "
+        "takes");
+  m.def("expr_adapt2d_source", &expr_adapt2d_source, py::arg("expr"),
+        "source of the adaptive 2-D kernels generated for an expression over x and y");
+  m.def("expr_adapt2d_compile", compiled(&expr_adapt2d_compile), py::arg("expr"),
+        "compile the adaptive 2-D kernels for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprAdaptive2D>(m, "ExprAdaptive2D",
+                             "the integral of f(x, y) over a rectangle to a requested tolerance "
+                             "(hipRTC, gfx950)")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("device") = 0)
+      .def("integrate",
+           [](ExprAdaptive2D& e, double ax, double bx, double ay, double by,
+              const Adapt2DOptions& o, uintptr_t out, uint64_t capacity) {
+             return e.integrate(ax, bx, ay, by, o, reinterpret_cast<double*>(out), capacity);
+           },
+           py::arg("ax"), py::arg("bx"), py::arg("ay"), py::arg("by"),
+           py::arg("options") = Adapt2DOptions(), py::arg("rects_out") = 0,
+           py::arg("capacity") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("time", &ExprAdaptive2D::time, py::arg("ax"), py::arg("bx"), py::arg("ay"),
+           py::arg("by"), py::arg("options"), py::arg("iters"),
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprAdaptive2D::expression);
+
   // adaptive sweeps: f(x, p0..p7) for K rows, each row to its own tolerance, in shared rounds
   m.attr("ADAPT_SWEEP_MAX_TOTAL_LIMIT") = kAdaptSweepMaxTotalLimit;
   m.attr("ADAPT_SWEEP_INITIAL_TOTAL") = kAdaptSweepInitialTotal;

@@ -228,6 +228,10 @@ def cmd_integrate(a) -> int:
 
         lo = 0.0 if a.a is None else a.a
         hi = 1.0 if a.b is None else a.b
+        if a.area_rtol is not None or a.area_atol is not None:
+            return _integrate_adaptive2d(a, lo, hi)
+        if a.panels_y is not None:
+            raise SystemExit("integrate: --panels-y belongs to --area-rtol / --area-atol")
         if a.row_rtol is not None or a.row_atol is not None:
             return _integrate_adaptive_sweep(a, lo, hi)
         if a.max_total is not None:
@@ -295,6 +299,9 @@ def cmd_integrate(a) -> int:
     if a.box:
         raise SystemExit("integrate: --box is the box of an --expr integrand over x0, x1, ...")
     _no_lattice_flags(a)
+    if a.area_rtol is not None or a.area_atol is not None or a.panels_y is not None:
+        raise SystemExit("integrate: --area-rtol / --area-atol are the tolerance of an --expr "
+                         "double integral")
     if a.row_rtol is not None or a.row_atol is not None or a.max_total is not None:
         raise SystemExit("integrate: --row-rtol / --row-atol are the per-row tolerance of an "
                          "--expr parameter sweep")
@@ -408,6 +415,67 @@ def _integrate_adaptive(a, lo: float, hi: float) -> int:
               f"(capped {int(r.capped)}, nonfinite {r.nonfinite}, forced {r.forced})",
               file=sys.stderr)
     rec = _json_ends(r.as_dict())
+    rec["value_bits"] = "%016x" % int.from_bytes(__import__("struct").pack("<d", r.value),
+                                                 "little")
+    if a.analytic is not None:
+        rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
+    print(json.dumps(rec))
+    return 0
+
+
+def _integrate_adaptive2d(a, lo: float, hi: float) -> int:
+    """integrate --expr E --ya AY --yb BY --area-rtol R / --area-atol T: the double integral to a
+    tolerance (one GPU, one rank). Whatever belongs to another mode is refused before anything
+    runs."""
+    import math
+    import os
+
+    from . import integrate_expr2d_adaptive
+
+    who = "--area-rtol / --area-atol"
+    if a.ya is None or a.yb is None:
+        raise SystemExit(f"integrate: {who} are the tolerance of a double integral: they need "
+                         "--ya AY --yb BY")
+    if a.rtol is not None or a.atol is not None:
+        raise SystemExit(f"integrate: {who} are the tolerance of a double integral: --rtol / "
+                         "--atol do not go with them")
+    if a.row_rtol is not None or a.row_atol is not None or a.max_total is not None:
+        raise SystemExit(f"integrate: {who} are the tolerance of a double integral: --row-rtol / "
+                         "--row-atol do not go with them")
+    given = {"--n": a.n is not None, "--ny": a.ny is not None, "--rule": a.rule is not None,
+             "--params": bool(a.params), "--linspace": bool(a.linspace), "--box": bool(a.box)}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: {who} choose the samples themselves: {flag} does not "
+                             "go with them")
+    _no_lattice_flags(a)
+    if a.device == "cpu" or a.backend != "hip":
+        which = "--device cpu" if a.device == "cpu" else f"--backend {a.backend}"
+        raise SystemExit(f"integrate: {who} have no host engine: {which} does not go with them")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"integrate: {who} run as one rank: a rank environment "
+                         f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
+    for flag, v in (("--a", lo), ("--b", hi), ("--ya", a.ya), ("--yb", a.yb)):
+        if math.isinf(v):
+            raise SystemExit(f"integrate: {flag} {v}: {who} integrate over a finite rectangle "
+                             "(no infinite side)")
+    opts = {k: v for k, v in (("rtol", a.area_rtol), ("atol", a.area_atol),
+                              ("panels_x", a.panels),
+                              ("panels_y", a.panels if a.panels_y is None else a.panels_y),
+                              ("max_depth", a.max_depth), ("max_intervals", a.max_intervals))
+            if v is not None}
+    try:
+        r = integrate_expr2d_adaptive(a.expr, lo, hi, a.ya, a.yb, **opts)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    if not r.converged:
+        print(f"integrate: not converged: err_est {r.err_est:.3g} against tol {r.tol:.3g} "
+              f"(capped {int(r.capped)}, nonfinite {r.nonfinite}, forced {r.forced})",
+              file=sys.stderr)
+    if not a.json:
+        print(f"{r.value:.17g}")
+        return 0
+    rec = r.as_dict()
     rec["value_bits"] = "%016x" % int.from_bytes(__import__("struct").pack("<d", r.value),
                                                  "little")
     if a.analytic is not None:
@@ -603,6 +671,16 @@ def main(argv=None) -> int:
                     "intervals to start from (65536)")
     ig.add_argument("--max-depth", type=int, default=None, help="bisections of one interval (60)")
     ig.add_argument("--max-intervals", type=int, default=None, help="intervals in all (2^22)")
+    ig.add_argument("--area-rtol", type=float, default=None, help="with --expr and --ya / --yb: "
+                    "the double integral over the finite rectangle to the tolerance "
+                    "max(area-atol, area-rtol |value|): the (7, 15) x (7, 15) product on rectangles "
+                    "bisected along the axis with the larger error (one GPU, one rank); prints the "
+                    "value, --json the record. --panels P and --panels-y Q (64, Q defaults to P) "
+                    "are then the first grid, --max-depth is per axis. An indicator's curve runs "
+                    "to the cap and reports capped")
+    ig.add_argument("--area-atol", type=float, default=None)
+    ig.add_argument("--panels-y", type=int, default=None, help="--area-rtol / --area-atol: the "
+                    "equal parts along y to start from (default: --panels)")
     ig.add_argument("--row-rtol", type=float, default=None, help="with --expr and --params / "
                     "--linspace: every row to its own tolerance max(row-atol, row-rtol |value of "
                     "the row|), the rows sharing the rounds (one GPU, one rank); --panels and "

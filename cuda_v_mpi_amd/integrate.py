@@ -606,6 +606,82 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
 
 
 @dataclasses.dataclass
+class Adaptive2DResult:
+    value: float
+    err_est: float          # the sum of the accepted rectangles' |K15xK15 - G7xG7|
+    resabs: float           # the rule's integral of |f|
+    tol: float              # the last round's tolerance, max(atol, rtol * |value so far|)
+    converged: bool         # err_est <= tol, not capped, no non-finite rectangle
+    evals: int              # 225 x rectangles evaluated
+    rounds: int
+    intervals: int          # the rectangles of the final partition
+    splits: int
+    splits_x: int           # bisections along x; splits = splits_x + splits_y
+    splits_y: int
+    floor: int              # accepted because the difference is rounding noise
+    forced: int             # accepted at the axis's max_depth, or too narrow to bisect
+    nonfinite: int
+    capped: bool            # the partition would have passed max_intervals
+    device_ms: float        # the rounds (hip) or the model's run (cpu), in ms
+    expr: str
+    ax: float
+    bx: float
+    ay: float
+    by: float
+    backend: str
+
+    def as_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+_ADAPT2D_FIELDS = ("value", "err_est", "resabs", "tol", "converged", "evals", "rounds",
+                   "intervals", "splits", "splits_x", "splits_y", "floor", "forced", "nonfinite",
+                   "capped")
+
+
+def integrate_expr2d_adaptive(expr: str, ax: float, bx: float, ay: float, by: float,
+                              rtol: float = 1e-10, atol: float = 0.0, panels_x: int = 64,
+                              panels_y: int = 64, max_depth: int = 60,
+                              max_intervals: int = 1 << 22,
+                              backend: str = "hip") -> Adaptive2DResult:
+    """The double integral of any f(x, y) given as one C++ expression over ``x`` and ``y`` on the
+    finite rectangle [ax, bx] x [ay, by] to the tolerance max(atol, rtol * |value|), with an
+    error estimate and a ``converged`` flag: the (7, 15) x (7, 15) Gauss-Kronrod product on
+    rectangles, each bisected along the axis that carries more of its error.
+    ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr2d``), one GPU.
+    ``backend="cpu"``: the numpy model of the same rule (``utils.adaptive_quad2d``) on
+    ``expr_torch``'s evaluation of the expression (its subset of expressions); needs no GPU.
+    One rank, one f(x, y), finite sides. A discontinuity along a curve (an indicator) is never
+    within its share of the tolerance: such a run ends ``capped``."""
+    ax, bx, ay, by = float(ax), float(bx), float(ay), float(by)
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr2d(expr, ax, bx, ay, by, rtol=rtol, atol=atol,
+                                panels=(int(panels_x), int(panels_y)), max_depth=max_depth,
+                                max_intervals=max_intervals)
+        fields = {k: getattr(r, k) for k in _ADAPT2D_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        from .utils.adaptive_quad2d import adaptive2d_model
+
+        def f(x, y):
+            return expr_torch(expr, torch.from_numpy(np.ascontiguousarray(x)),
+                              torch.from_numpy(np.ascontiguousarray(y))).numpy()
+
+        t0 = time.perf_counter()
+        r = adaptive2d_model(f, ax, bx, ay, by, rtol=rtol, atol=atol, panels_x=int(panels_x),
+                             panels_y=int(panels_y), max_depth=int(max_depth),
+                             max_intervals=int(max_intervals))
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in _ADAPT2D_FIELDS}
+    else:
+        raise ValueError("integrate_expr2d_adaptive backend must be 'hip' or 'cpu'")
+    return Adaptive2DResult(**fields, device_ms=ms, expr=expr, ax=ax, bx=bx, ay=ay, by=by,
+                            backend=backend)
+
+
+@dataclasses.dataclass
 class AdaptiveSweepResult:
     """Per row (numpy arrays of K entries, fields as in ``AdaptiveResult``), then the call."""
     value: "np.ndarray"

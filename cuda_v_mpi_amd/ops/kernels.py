@@ -518,6 +518,42 @@ def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 
     return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
 
 
+_EXPR_ADAPT2D_CACHE: dict = {}
+
+
+def quad_expr2d(expr: str, ax: float, bx: float, ay: float, by: float, rtol: float = 1e-10,
+                atol: float = 0.0, panels=64, max_depth: int = 60,
+                max_intervals: int = 1 << 22, return_rects: bool = False):
+    """The double integral of any f(x, y) given as one C++ expression over ``x`` and ``y`` on the
+    finite rectangle [ax, bx] x [ay, by] to the tolerance max(atol, rtol * |value|): the tensor
+    product of the Gauss-Kronrod (7, 15) pair (225 evaluations a rectangle) from ``panels`` equal
+    rectangles (one number for both axes or a pair (panels_x, panels_y)), each bisected by rounds
+    along the axis that carries more of its error where the estimate misses its share (at most
+    ``max_depth`` times per axis, ``max_intervals`` rectangles in all), six hipRTC-compiled
+    gfx950 kernels cached with their module per (expression, device)
+    (csrc/runtime/expr_adaptive2d.cpp). Returns the native Adapt2DResult: value, err_est, resabs,
+    tol, converged, evals, rounds, intervals, splits, splits_x, splits_y, floor, forced,
+    nonfinite, capped, device_ms. With ``return_rects`` also the final partition as an fp64 device
+    tensor [n, 4] of (x0, x1, y0, y1), ordered by (y0, x0)."""
+    m = native()
+    px, py = (panels, panels) if isinstance(panels, int) else panels
+    opt = m.Adapt2DOptions(float(rtol), float(atol), int(px), int(py), int(max_depth),
+                           int(max_intervals))
+    m.adapt2d_check(float(ax), float(bx), float(ay), float(by), opt)  # before any device call
+    dev = _device()
+    key = (expr, dev.index)
+    ea = _EXPR_ADAPT2D_CACHE.get(key)
+    if ea is None:
+        ea = _EXPR_ADAPT2D_CACHE[key] = m.ExprAdaptive2D(expr, dev.index)
+    if not return_rects:
+        return ea.integrate(float(ax), float(bx), float(ay), float(by), opt)
+    rects = torch.empty((int(max_intervals), 4), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the rounds run on their own stream
+    r = ea.integrate(float(ax), float(bx), float(ay), float(by), opt, rects.data_ptr(),
+                     int(max_intervals))
+    return r, rects[:r.intervals]
+
+
 _EXPR_ADAPT_SWEEP_CACHE: dict = {}
 
 
