@@ -6,7 +6,8 @@ miint/expr.hpp in the same order, on the doubles of the rule's own table (``gk15
 its weights) and at the nodes the kernels form (``gk15_abscissae``: fma(hw, t_j, c)). What the
 model does not share with the device is the order of its sums (numpy's pairwise ``sum`` here,
 butterflies and fma chains there) and the math library behind f, so a value agrees to rounding,
-not bit for bit, and a decision on the border of a bound may fall the other way.
+not bit for bit, and a decision on the border of a bound may fall the other way. The reference
+that fixes bits, with the device's own order of every sum, is ``adaptive_exact.py`` beside it.
 
     r = adaptive_model(lambda x: 1.0 / (x * x + 1e-8), -1.0, 1.0, rtol=1e-10)
     r["value"], r["err_est"], r["converged"], r["lo"], r["hi"]
