@@ -41,6 +41,9 @@
 // With --params / --linspace and --row-rtol R and / or --row-atol T every row is integrated to
 // its own tolerance in shared rounds (ExprAdaptiveSweep): one line per row, or with --json the
 // per-row arrays and the call's fields; one warning with the number of rows not converged.
+// With --ya / --yb and --area-rtol R and / or --area-atol T the double integral is taken to that
+// tolerance (ExprAdaptive2D); with --y-lo EXPR --y-hi EXPR in place of --ya / --yb the limits in
+// y are expressions over x (ExprAdaptiveRegion): y between two curves.
 // With --box A0:B0,A1:B1,... the expression is over x0, x1, ... and its integral over the box is
 // taken by a randomly shifted rank-1 lattice rule (ExprLattice): --m M for the rule of 2^M
 // points, or --rtol / --atol for the walk over M; the ranks split the points.
@@ -560,11 +563,18 @@ bool area_adaptive_requested(const cli::Args& a) {
   return a.has("area-rtol") || a.has("area-atol");
 }
 bool row_adaptive_requested(const cli::Args& a);
+// --y-lo EXPR --y-hi EXPR in place of --ya / --yb: y between two curves (ExprAdaptiveRegion).
+bool region_requested(const cli::Args& a) { return a.has("y-lo") || a.has("y-hi"); }
 
 int run_expr_adaptive2d(const cli::Args& a, const RiemannConfig& cfg) {
   const std::string who = "--area-rtol / --area-atol";
-  MIINT_CHECK(a.has("ya") && a.has("yb"),
-              who + " are the tolerance of a double integral: they need --ya AY --yb BY");
+  const bool region = region_requested(a);
+  MIINT_CHECK(!region || (a.has("y-lo") && a.has("y-hi")),
+              "--y-lo and --y-hi go together (the two limits in y of a double integral): --" +
+                  std::string(a.has("y-lo") ? "y-hi" : "y-lo") + " is missing");
+  MIINT_CHECK(region || (a.has("ya") && a.has("yb")),
+              who + " are the tolerance of a double integral: they need --ya AY --yb BY (or "
+                    "--y-lo EXPR --y-hi EXPR)");
   MIINT_CHECK(!adaptive_requested(a), who + " are the tolerance of a double integral: --rtol / "
                                             "--atol do not go with them");
   MIINT_CHECK(!row_adaptive_requested(a), who + " are the tolerance of a double integral: "
@@ -595,14 +605,18 @@ int run_expr_adaptive2d(const cli::Args& a, const RiemannConfig& cfg) {
   o.panels_y = static_cast<uint64_t>(py);
   o.max_depth = static_cast<int>(depth);
   o.max_intervals = static_cast<uint64_t>(max_iv);
-  const double ya = a.num("ya", 0.0), yb = a.num("yb", 0.0);
+  // between two curves the rounds run on [a, b] x [0, 1] in (x, v): ya = 0, yb = 1
+  const double ya = region ? 0.0 : a.num("ya", 0.0), yb = region ? 1.0 : a.num("yb", 0.0);
   adapt2d_check(cfg.a, cfg.b, ya, yb, o);
   const std::string expr = a.str("expr", "");
-  (void)expr_adapt2d_source(expr);  // a rejected expression: before any device call
+  const std::string y_lo = a.str("y-lo", ""), y_hi = a.str("y-hi", "");
+  // a rejected expression: before any device call
+  if (region) (void)expr_region_source(expr, y_lo, y_hi);
+  else (void)expr_adapt2d_source(expr);
   MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
   set_device(0);
-  ExprAdaptive2D ea(expr, 0);
-  const Adapt2DResult r = ea.integrate(cfg.a, cfg.b, ya, yb, o);
+  const Adapt2DResult r = region ? ExprAdaptiveRegion(expr, y_lo, y_hi, 0).integrate(cfg.a, cfg.b, o)
+                                 : ExprAdaptive2D(expr, 0).integrate(cfg.a, cfg.b, ya, yb, o);
   const double secs = wall_seconds() - process_start_seconds();
   if (!r.converged)
     std::fprintf(stderr, "riemann: not converged: err_est %.3g against tol %.3g (capped %d, "
@@ -612,7 +626,9 @@ int run_expr_adaptive2d(const cli::Args& a, const RiemannConfig& cfg) {
   if (!a.flag("json")) std::printf("%.17g\n", r.value);
   cli::JsonRecord rec;
   rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
-      .add("ya", ya).add("yb", yb).add("rtol", o.rtol).add("atol", o.atol)
+      .add("ya", ya).add("yb", yb);
+  if (region) rec.add("y_lo", y_lo).add("y_hi", y_hi);
+  rec.add("rtol", o.rtol).add("atol", o.atol)
       .add("panels", static_cast<double>(o.panels_x))
       .add("panels_y", static_cast<double>(o.panels_y)).add("max_depth", o.max_depth)
       .add("max_intervals", static_cast<double>(o.max_intervals))
@@ -967,6 +983,8 @@ constexpr const char* kUsage =
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY [--n NX] [--ny NY] [--analytic V]]\n"
     "               [--expr EXPR --a AX --b BX --ya AY --yb BY --area-rtol R [--area-atol T]\n"
     "                [--panels P] [--panels-y Q] [--max-depth D] [--max-intervals M]]\n"
+    "               [--expr EXPR --a AX --b BX --y-lo EXPR --y-hi EXPR --area-rtol R [--area-atol T]\n"
+    "                [--panels P] [--panels-y Q] [--max-depth D] [--max-intervals M]]\n"
     "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
     "                [--max-intervals M]]\n"
     "               [--expr EXPR --a A --b B --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
@@ -994,7 +1012,16 @@ constexpr const char* kUsage =
     "  refused without --ya / --yb, with --n, --ny, --rule, --running, --params, --linspace, --box,\n"
     "  --rtol, --atol, --row-rtol, --row-atol, --gpus above 1, --loopback, WORLD_SIZE above 1 or\n"
     "  --device cpu, and with an infinite side. A discontinuity along a curve (an indicator) runs\n"
-    "  to the cap and reports capped: use the fixed rule or --box there.\n"
+    "  to the cap and reports capped: use --y-lo / --y-hi, the fixed rule or --box there.\n"
+    "--y-lo EXPR --y-hi EXPR: with --area-rtol R / --area-atol T and in place of --ya / --yb, the\n"
+    "  double integral of --expr over AX <= x <= BX, y_lo(x) <= y <= y_hi(x), both limits\n"
+    "  expressions over x alone (write --y-lo=-sqrt(1.0-x*x) where one begins with a minus). The\n"
+    "  region is mapped onto [AX, BX] x [0, 1] by y = y_lo + (y_hi - y_lo) v and the rounds above\n"
+    "  run on f (y_hi - y_lo): err_est, resabs and tol are the mapped integrand's, --panels-y\n"
+    "  divides v. Where y_hi(x) < y_lo(x) the strip counts negatively; a limit that is not finite\n"
+    "  at a node counts as nonfinite. The outputs are those of the rectangle form (ya 0, yb 1);\n"
+    "  --json adds y_lo, y_hi. Refused with one limit alone, without --area-rtol / --area-atol,\n"
+    "  with --ya / --yb, with a y in a limit and with whatever --area-rtol refuses.\n"
     "--rtol R / --atol T: the integral of --expr on [A, B] to the tolerance max(T, R |value|)\n"
     "  (adaptive Gauss-Kronrod (7, 15) from --panels P equal intervals, default 65536, bisected at\n"
     "  most --max-depth D times, default 60, at most --max-intervals M in all, default 2^22);\n"
@@ -1079,9 +1106,12 @@ int main(int argc, char** argv) {
                 "--running is the running integral of an --expr integrand");
     MIINT_CHECK(a.flag("running") || !(a.has("every") || a.has("running-out")),
                 "--every / --running-out belong to --running");
+    MIINT_CHECK(!region_requested(a) || !(a.has("ya") || a.has("yb")),
+                "--y-lo / --y-hi are the limits in y as expressions over x: --ya / --yb (the "
+                "limits as numbers) do not go with them");
     MIINT_CHECK(a.has("ya") == a.has("yb"),
                 "--ya and --yb go together: the y interval of a double integral");
-    MIINT_CHECK(a.has("ya") || !a.has("ny"),
+    MIINT_CHECK(a.has("ya") || region_requested(a) || !a.has("ny"),
                 "--ny belongs to a double integral (--ya AY --yb BY)");
     MIINT_CHECK(a.has("expr") || !a.has("ya"),
                 "--ya / --yb are the double integral of an --expr integrand over x and y");
@@ -1091,6 +1121,11 @@ int main(int argc, char** argv) {
                 "--row-rtol / --row-atol are the per-row tolerance of an --expr parameter sweep");
     MIINT_CHECK(a.has("expr") || !area_adaptive_requested(a),
                 "--area-rtol / --area-atol are the tolerance of an --expr double integral");
+    MIINT_CHECK(a.has("expr") || !region_requested(a),
+                "--y-lo / --y-hi are the limits in y of an --expr double integral");
+    MIINT_CHECK(area_adaptive_requested(a) || !region_requested(a),
+                "--y-lo / --y-hi are the limits of a double integral to a tolerance: they need "
+                "--area-rtol R / --area-atol T (the fixed rule has no such region)");
     MIINT_CHECK(area_adaptive_requested(a) || !a.has("panels-y"),
                 "--panels-y belongs to --area-rtol / --area-atol");
     MIINT_CHECK(adaptive_requested(a) || row_adaptive_requested(a) || area_adaptive_requested(a) ||

@@ -623,6 +623,8 @@ class ExprAdaptive2D {
   const std::string& expression() const { return expr_; }
 
  private:
+  friend class ExprAdaptiveRegion;  // the same rounds and buffers around another evaluation kernel
+  ExprAdaptive2D(const std::string& expr, const std::string& code, const char* eval, int device);
   void reserve(uint64_t max_intervals);
   Adapt2DResult rounds(double x0, double x1, double y0, double y1, const Adapt2DOptions& opt,
                        double* out, uint64_t cap);
@@ -641,6 +643,64 @@ class ExprAdaptive2D {
   PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
   Event e0_, e1_;
   detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+};
+
+// ---------------------------------------------------------------------------------------
+// Adaptive double integrals between two curves: the integral of f(x, y) over the region
+// { ax <= x <= bx, g(x) <= y <= h(x) } to max(atol, rtol |value|), g = ylo and h = yhi two more
+// run-time expressions over x alone.
+//
+// The region is mapped onto (x, v) in [ax, bx] x [0, 1] by y = g(x) + (h(x) - g(x)) v, and
+// ExprAdaptive2D's rounds run on the mapped integrand f(x, y(x, v)) (h(x) - g(x)) over that
+// rectangle. A rectangle of the list is [x0, x1] x [v0, v1]; the list starts as panels_x x
+// panels_y equal rectangles of [min(ax, bx), max(ax, bx)] x [0, 1], formed by
+// miint_adapt2d_init. Per rectangle (expr_adaptive_region.cpp, miint_region_gk15x15):
+//   the x nodes x_i are ExprAdaptive2D's: cx and fma(hx, -+t_i, cx); the v nodes v_j are what it
+//   forms along y: cy and fma(hy, -+t_j, cy).
+//   Per x node, once per rectangle and in front of the loop over the rows:
+//     g_i = ylo(x_i),  w_i = yhi(x_i) - g_i.
+//   Per node pair: y_ij = fma(w_i, v_j, g_i), and the value summed is f(x_i, y_ij) * w_i.
+//   Contraction is off around the subtraction and the product, as in miint_gk15x15.
+// Everything after the 225 values is ExprAdaptive2D's with Wx = |bx - ax| and Wy = 1: the row
+// sums, the row combination, K, err, ex, ey, R, the split axis, the decision order, the depths,
+// the cap and the eighteen-word record. Of a round's six kernels only the evaluation kernel has
+// a twin (miint_region_eval); the other five are the text ExprAdaptive2D compiles.
+//
+// ax > bx negates; ax == bx gives 0 with no launch. Where h(x) < g(x), w_i is negative and that
+// strip counts negatively: the pointwise form of ay > by, neither refused nor clamped. A limit
+// that is not finite at a node makes that rectangle `nonfinite`, as a non-finite f does.
+// err_est, resabs and tol are those of the mapped integrand: resabs is the rule's integral of
+// |f (h - g)|. With rects_out the partition is in (x, v), ordered by (v0, x0).
+// Left out: limits in x that depend on y (swap the names), infinite sides, parameter rows, more
+// than one rank, a host engine. A limit: a singularity of f on the boundary curve itself
+// evaluates 0 * inf at nodes where w_i rounds to 0 and the run reports `nonfinite`
+// (1.0/sqrt(y) over the upper half disc); one strictly inside the region that the map does not
+// remove (1.0/sqrt(x*x+y*y) over the whole disc) runs to the cap: split the region there.
+// ---------------------------------------------------------------------------------------
+// Throws unless all three pass expr_check (naming which of the three it is and the expression)
+// and neither limit mentions the identifier y.
+std::string expr_region_source(const std::string& expr, const std::string& ylo,
+                               const std::string& yhi);
+// hipRTC compile for gfx950 (no device needed), cached per source.
+std::string expr_region_compile(const std::string& expr, const std::string& ylo,
+                                const std::string& yhi);
+
+class ExprAdaptiveRegion {
+ public:
+  ExprAdaptiveRegion(const std::string& expr, const std::string& ylo, const std::string& yhi,
+                     int device = 0);
+  // As ExprAdaptive2D::integrate on [ax, bx] x [0, 1] in (x, v); the options are checked by
+  // adapt2d_check with ay = 0, by = 1. rects_out takes (x0, x1, v0, v1), ordered by (v0, x0).
+  Adapt2DResult integrate(double ax, double bx, const Adapt2DOptions& opt = {},
+                          double* rects_out = nullptr, uint64_t capacity = 0);
+  double time(double ax, double bx, const Adapt2DOptions& opt, int iters);
+  const std::string& expression() const { return rounds_.expression(); }
+  const std::string& y_lo() const { return ylo_; }
+  const std::string& y_hi() const { return yhi_; }
+
+ private:
+  std::string ylo_, yhi_;
+  ExprAdaptive2D rounds_;  // its buffers and rounds around miint_region_eval
 };
 
 // ---------------------------------------------------------------------------------------

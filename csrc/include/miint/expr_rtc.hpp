@@ -35,6 +35,18 @@ std::string adapt_rule_source(const std::string& expr, const std::string& sig,
 std::string adapt_unbounded_rule_source(const std::string& expr, const std::string& sig,
                                         const std::string& args);
 
+// The adaptive 2-D families' shared device text (expr_adaptive2d.cpp): ExprAdaptive2D's source is
+// the prelude, miint_f, the table, the row macros and miint_gk15x15 (its row loop printed by
+// adapt2d_row_source, closed by kAdapt2DCombine), kAdapt2DInit, the evaluation kernel and
+// kAdapt2DRound. ExprAdaptiveRegion replaces the function, the macros, the rule and the
+// evaluation kernel and carries the rest as it stands. adapt2d_row_source(true) also passes a
+// pair's two column numbers to its macro.
+std::string adapt2d_table_source();
+std::string adapt2d_row_source(bool columns);
+extern const char* const kAdapt2DCombine;
+extern const char* const kAdapt2DInit;
+extern const char* const kAdapt2DRound;
+
 // A loaded code object and its kernels. The destructor selects the device, drains the owning
 // object's stream and unloads: declare it as the owner's LAST member, after the Stream, the
 // buffers and the events, so that member order destroys it first (nothing a kernel may still

@@ -1209,6 +1209,35 @@ PYBIND11_MODULE(_miint, m) {
            py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprAdaptive2D::expression);
 
+  // adaptive double integrals between two curves: y from ylo(x) to yhi(x)
+  m.def("expr_region_source", &expr_region_source, py::arg("expr"), py::arg("ylo"),
+        py::arg("yhi"),
+        "source of the adaptive region kernels generated for f(x, y) and the two limits in y, "
+        "expressions over x");
+  m.def("expr_region_compile", compiled(&expr_region_compile), py::arg("expr"), py::arg("ylo"), py::arg("yhi"),
+        "compile the adaptive region kernels for gfx950 with hipRTC (no device needed)");
+  m.def("fma", py::vectorize([](double a, double b, double c) { return std::fma(a, b, c); }),
+        py::arg("a"), py::arg("b"), py::arg("c"),
+        "fma(a, b, c) element by element, rounded once: the y the region kernels form");
+  py::class_<ExprAdaptiveRegion>(m, "ExprAdaptiveRegion",
+                                 "the integral of f(x, y) for y between two curves ylo(x) and "
+                                 "yhi(x) to a requested tolerance (hipRTC, gfx950)")
+      .def(py::init<const std::string&, const std::string&, const std::string&, int>(),
+           py::arg("expr"), py::arg("ylo"), py::arg("yhi"), py::arg("device") = 0)
+      .def("integrate",
+           [](ExprAdaptiveRegion& e, double ax, double bx, const Adapt2DOptions& o, uintptr_t out,
+              uint64_t capacity) {
+             return e.integrate(ax, bx, o, reinterpret_cast<double*>(out), capacity);
+           },
+           py::arg("ax"), py::arg("bx"), py::arg("options") = Adapt2DOptions(),
+           py::arg("rects_out") = 0, py::arg("capacity") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("time", &ExprAdaptiveRegion::time, py::arg("ax"), py::arg("bx"), py::arg("options"),
+           py::arg("iters"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprAdaptiveRegion::expression)
+      .def_property_readonly("y_lo", &ExprAdaptiveRegion::y_lo)
+      .def_property_readonly("y_hi", &ExprAdaptiveRegion::y_hi);
+
   // adaptive sweeps: f(x, p0..p7) for K rows, each row to its own tolerance, in shared rounds
   m.attr("ADAPT_SWEEP_MAX_TOTAL_LIMIT") = kAdaptSweepMaxTotalLimit;
   m.attr("ADAPT_SWEEP_INITIAL_TOTAL") = kAdaptSweepInitialTotal;

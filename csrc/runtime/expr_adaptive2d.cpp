@@ -74,37 +74,61 @@ void adapt2d_check(double ax, double bx, double ay, double by, const Adapt2DOpti
               what + "max_depth = " + std::to_string(o.max_depth) + " must be 0..200 (per axis)");
 }
 
+namespace detail {
+
+namespace {
+// The rule's one table (gk15_nodes and its weights): the non-negative nodes from the centre
+// outwards, their Kronrod weights, and the Gauss weights of nodes 0, 2, 4, 6.
+struct Gk15Table {
+  double t[8], wk[8], wg[4];
+  Gk15Table() {
+    const std::vector<double> t15 = gk15_nodes(), wk15 = gk15_weights(), wg7 = gk7_weights();
+    for (int j = 0; j < 8; ++j) {
+      t[j] = t15[7 + j];
+      wk[j] = wk15[7 + j];
+    }
+    for (int j = 0; j < 4; ++j) wg[j] = wg7[3 + j];
+  }
+};
+}  // namespace
+
+std::string adapt2d_table_source() {
+  const Gk15Table g;
+  return R"(
+// The y direction's table, read with a wave-uniform index: scalar loads.
+__constant__ double miint_gk_t[8] = )" + table(g.t, 8) + R"(;
+__constant__ double miint_gk_wk[8] = )" + table(g.wk, 8) + R"(;
+__constant__ double miint_gk_wg[4] = )" + table(g.wg, 4) + R"(;
+)";
+}
+
+// A row's fifteen evaluations, printed: the centre, then a pair of nodes per line. With
+// `columns` a pair's macro also takes the numbers of its two columns, 2 j - 1 and 2 j.
+std::string adapt2d_row_source(bool columns) {
+  const Gk15Table g;
+  std::string row = "    MIINT_ROW_CENTRE(" + hex(g.wk[0]) + ", " + hex(g.wg[0]) + ")\n";
+  for (int j = 1; j < 8; ++j) {
+    const std::string cols =
+        columns ? ", " + std::to_string(2 * j - 1) + ", " + std::to_string(2 * j) : "";
+    if (j % 2 == 0)
+      row += "    MIINT_ROW_GAUSS_PAIR(" + hex(g.t[j]) + ", " + hex(g.wk[j]) + ", " +
+             hex(g.wg[j / 2]) + cols + ")\n";
+    else
+      row += "    MIINT_ROW_PAIR(" + hex(g.t[j]) + ", " + hex(g.wk[j]) + cols + ")\n";
+  }
+  return row;
+}
+
+}  // namespace detail
+
 std::string expr_adapt2d_source(const std::string& expr) {
   detail::expr_check_named(expr);
-  // the rule's one table (gk15_nodes and its weights): the non-negative nodes from the centre
-  // outwards, their Kronrod weights, and the Gauss weights of nodes 0, 2, 4, 6
-  const std::vector<double> t15 = gk15_nodes(), wk15 = gk15_weights(), wg7 = gk7_weights();
-  double t[8], wk[8], wg[4];
-  for (int j = 0; j < 8; ++j) {
-    t[j] = t15[7 + j];
-    wk[j] = wk15[7 + j];
-  }
-  for (int j = 0; j < 4; ++j) wg[j] = wg7[3 + j];
-  // a row's fifteen evaluations, printed: the centre, then a pair of nodes per line
-  std::string row = "    MIINT_ROW_CENTRE(" + hex(wk[0]) + ", " + hex(wg[0]) + ")\n";
-  for (int j = 1; j < 8; ++j) {
-    if (j % 2 == 0)
-      row += "    MIINT_ROW_GAUSS_PAIR(" + hex(t[j]) + ", " + hex(wk[j]) + ", " + hex(wg[j / 2]) +
-             ")\n";
-    else
-      row += "    MIINT_ROW_PAIR(" + hex(t[j]) + ", " + hex(wk[j]) + ")\n";
-  }
   return std::string(detail::kRtcPrelude) + R"(
 __device__ __forceinline__ double miint_f(double x, double y) {
   (void)x; (void)y;
   return ()" + expr + R"();
 }
-
-// The y direction's table, read with a wave-uniform index: scalar loads.
-__constant__ double miint_gk_t[8] = )" + table(t, 8) + R"(;
-__constant__ double miint_gk_wk[8] = )" + table(wk, 8) + R"(;
-__constant__ double miint_gk_wg[4] = )" + table(wg, 4) + R"(;
-
+)" + detail::adapt2d_table_source() + R"(
 // One row of the (7, 15) x (7, 15) product at a fixed y: f at the centre cx and at the seven
 // pairs fma(hx, -+t, cx), from the centre outwards, the three row sums carried by fma.
 #define MIINT_ROW_CENTRE(wk, wg) \
@@ -135,7 +159,34 @@ __device__ __forceinline__ void miint_gk15x15(double2 xr, double2 yr, double* k,
     const double t = miint_gk_t[j];
     const double y = row == 0 ? cy : fma(hy, (row & 1) ? -t : t, cy);
     double rk, rg, ra;
-)" + row + R"(    if (row == 0) {
+)" + detail::adapt2d_row_source(false) + detail::kAdapt2DCombine + detail::kAdapt2DInit + R"(
+// One rectangle per lane: the same 225 evaluations in every lane, 16-byte extent loads.
+extern "C" __global__ __launch_bounds__(256) void miint_adapt2d_eval(
+    unsigned long long n, const double2* __restrict__ xs, const double2* __restrict__ ys,
+    double* __restrict__ k, double* __restrict__ err, double2* __restrict__ dir,
+    double* __restrict__ r, double* __restrict__ part_k) {
+  __shared__ double red[4];
+  const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  double v = 0.0;
+  if (i < n) {
+    double e, ex, ey, a;
+    miint_gk15x15(xs[i], ys[i], &v, &e, &ex, &ey, &a);
+    k[i] = v;
+    err[i] = e;
+    dir[i] = make_double2(ex, ey);
+    r[i] = a;
+  }
+  MIINT_BLOCK_SUM(v, red);
+  if (threadIdx.x == 0) part_k[blockIdx.x] = MIINT_RED(red);
+}
+)" + detail::kAdapt2DRound;
+}
+
+namespace detail {
+
+// The end of a row of the rule's loop and of the rule: the row's three sums onto the five of
+// the rectangle, then K, err, ex, ey and R. Shared by miint_gk15x15 and its region twin.
+const char* const kAdapt2DCombine = R"(    if (row == 0) {
       const double wk = miint_gk_wk[0], wg = miint_gk_wg[0];
       kk = wk * rk; gk = wk * rg; aa = wk * ra;
       gg = wg * rg; kg = wg * rk;
@@ -159,7 +210,11 @@ __device__ __forceinline__ void miint_gk15x15(double2 xr, double2 yr, double* k,
   *ey = fabs(kv - s * kg);
   *r = s * aa;
 }
+)";
 
+// The kernels of a round that do not evaluate f: miint_adapt2d_init in front of the evaluation
+// kernel, the other four behind it. ExprAdaptiveRegion's source carries the same text.
+const char* const kAdapt2DInit = R"(
 // st[0..7] as doubles: S_acc, E_acc, R_acc, tol, sum_K; st[8..17]: accepted, splits, floor,
 // forced, nonfinite, next, capped, base (the rectangles accepted before this round), splits_x,
 // splits_y.
@@ -182,27 +237,9 @@ extern "C" __global__ __launch_bounds__(256) void miint_adapt2d_init(
   ys[i] = make_double2(y0, y1);
   depth[i] = 0u;
 }
+)";
 
-// One rectangle per lane: the same 225 evaluations in every lane, 16-byte extent loads.
-extern "C" __global__ __launch_bounds__(256) void miint_adapt2d_eval(
-    unsigned long long n, const double2* __restrict__ xs, const double2* __restrict__ ys,
-    double* __restrict__ k, double* __restrict__ err, double2* __restrict__ dir,
-    double* __restrict__ r, double* __restrict__ part_k) {
-  __shared__ double red[4];
-  const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  double v = 0.0;
-  if (i < n) {
-    double e, ex, ey, a;
-    miint_gk15x15(xs[i], ys[i], &v, &e, &ex, &ey, &a);
-    k[i] = v;
-    err[i] = e;
-    dir[i] = make_double2(ex, ey);
-    r[i] = a;
-  }
-  MIINT_BLOCK_SUM(v, red);
-  if (threadIdx.x == 0) part_k[blockIdx.x] = MIINT_RED(red);
-}
-
+const char* const kAdapt2DRound = R"(
 // sum_K over the nb workgroups' partials, then the round's tolerance. A NaN sum gives a NaN
 // tolerance (atol > NaN is false).
 extern "C" __global__ __launch_bounds__(256) void miint_adapt2d_close(
@@ -420,17 +457,24 @@ extern "C" __global__ __launch_bounds__(256) void miint_adapt2d_scatter(
   }
 }
 )";
-}
+
+}  // namespace detail
 
 std::string expr_adapt2d_compile(const std::string& expr) {
   return detail::rtc_compile_cached(expr_adapt2d_source(expr), expr);
 }
 
 ExprAdaptive2D::ExprAdaptive2D(const std::string& expr, int device)
+    : ExprAdaptive2D(expr, expr_adapt2d_compile(expr), "miint_adapt2d_eval", device) {}
+
+// `code` holds the five kernels every round shares and the evaluation kernel `eval`, which
+// takes miint_adapt2d_eval's arguments.
+ExprAdaptive2D::ExprAdaptive2D(const std::string& expr, const std::string& code, const char* eval,
+                               int device)
     : expr_(expr), device_(device), stream_((set_device(device), Stream())),
-      module_(expr_adapt2d_compile(expr), device, stream_,
-              {"miint_adapt2d_init", "miint_adapt2d_eval", "miint_adapt2d_close",
-               "miint_adapt2d_decide", "miint_adapt2d_prefix", "miint_adapt2d_scatter"}) {
+      module_(code, device, stream_,
+              {"miint_adapt2d_init", eval, "miint_adapt2d_close", "miint_adapt2d_decide",
+               "miint_adapt2d_prefix", "miint_adapt2d_scatter"}) {
   DeviceGuard g(device);
   state_ = DeviceBuffer<unsigned long long>(kStateWords);
   record_ = PinnedBuffer<unsigned long long>(kStateWords);

@@ -28,7 +28,9 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     ``ops.kernels.quad_expr_sweep``, ``riemann --expr ... --params FILE --row-rtol R``), and
     the double integral of f(x, y) over a rectangle to a tolerance
     (``integrate_expr2d_adaptive``, ``ops.kernels.quad_expr2d``,
-    ``riemann --expr ... --ya AY --yb BY --area-rtol R``), and
+    ``riemann --expr ... --ya AY --yb BY --area-rtol R``) or between two curves, y from
+    y_lo(x) to y_hi(x) (``integrate_expr2d_region``, ``ops.kernels.quad_expr2d_region``,
+    ``riemann --expr ... --y-lo EXPR --y-hi EXPR --area-rtol R``), and
     its integral over a box in up to 16 variables by
     a randomly shifted lattice rule (``integrate_expr_nd``, ``ops.kernels.lattice_expr``,
     ``riemann --expr ... --box 0:1,0:1,0:3 --m 20``).
@@ -48,5 +50,6 @@ from .integrate import integrate_expr2d  # noqa: F401
 from .integrate import AdaptiveResult, integrate_expr_adaptive  # noqa: F401
 from .integrate import AdaptiveSweepResult, integrate_expr_adaptive_sweep  # noqa: F401
 from .integrate import Adaptive2DResult, integrate_expr2d_adaptive  # noqa: F401
+from .integrate import AdaptiveRegionResult, integrate_expr2d_region  # noqa: F401
 from .integrate import LatticeResult, integrate_expr_nd  # noqa: F401
 from .models import integrands  # noqa: F401

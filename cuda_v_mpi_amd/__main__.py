@@ -230,6 +230,10 @@ def cmd_integrate(a) -> int:
         hi = 1.0 if a.b is None else a.b
         if a.area_rtol is not None or a.area_atol is not None:
             return _integrate_adaptive2d(a, lo, hi)
+        if a.y_lo is not None or a.y_hi is not None:
+            raise SystemExit("integrate: --y-lo / --y-hi are the limits of a double integral to a "
+                             "tolerance: they need --area-rtol R / --area-atol T (the fixed rule "
+                             "has no such region)")
         if a.panels_y is not None:
             raise SystemExit("integrate: --panels-y belongs to --area-rtol / --area-atol")
         if a.row_rtol is not None or a.row_atol is not None:
@@ -299,6 +303,9 @@ def cmd_integrate(a) -> int:
     if a.box:
         raise SystemExit("integrate: --box is the box of an --expr integrand over x0, x1, ...")
     _no_lattice_flags(a)
+    if a.y_lo is not None or a.y_hi is not None:
+        raise SystemExit("integrate: --y-lo / --y-hi are the limits in y of an --expr double "
+                         "integral")
     if a.area_rtol is not None or a.area_atol is not None or a.panels_y is not None:
         raise SystemExit("integrate: --area-rtol / --area-atol are the tolerance of an --expr "
                          "double integral")
@@ -425,17 +432,25 @@ def _integrate_adaptive(a, lo: float, hi: float) -> int:
 
 def _integrate_adaptive2d(a, lo: float, hi: float) -> int:
     """integrate --expr E --ya AY --yb BY --area-rtol R / --area-atol T: the double integral to a
-    tolerance (one GPU, one rank). Whatever belongs to another mode is refused before anything
-    runs."""
+    tolerance (one GPU, one rank); with --y-lo EXPR --y-hi EXPR in place of --ya / --yb, y between
+    two curves. Whatever belongs to another mode is refused before anything runs."""
     import math
     import os
 
     from . import integrate_expr2d_adaptive
 
     who = "--area-rtol / --area-atol"
-    if a.ya is None or a.yb is None:
+    region = a.y_lo is not None or a.y_hi is not None
+    if region and (a.y_lo is None or a.y_hi is None):
+        missing = "--y-hi" if a.y_hi is None else "--y-lo"
+        raise SystemExit("integrate: --y-lo and --y-hi go together (the two limits in y of a "
+                         f"double integral): {missing} is missing")
+    if region and (a.ya is not None or a.yb is not None):
+        raise SystemExit("integrate: --y-lo / --y-hi are the limits in y as expressions over x: "
+                         "--ya / --yb (the limits as numbers) do not go with them")
+    if not region and (a.ya is None or a.yb is None):
         raise SystemExit(f"integrate: {who} are the tolerance of a double integral: they need "
-                         "--ya AY --yb BY")
+                         "--ya AY --yb BY (or --y-lo EXPR --y-hi EXPR)")
     if a.rtol is not None or a.atol is not None:
         raise SystemExit(f"integrate: {who} are the tolerance of a double integral: --rtol / "
                          "--atol do not go with them")
@@ -456,7 +471,7 @@ def _integrate_adaptive2d(a, lo: float, hi: float) -> int:
         raise SystemExit(f"integrate: {who} run as one rank: a rank environment "
                          f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
     for flag, v in (("--a", lo), ("--b", hi), ("--ya", a.ya), ("--yb", a.yb)):
-        if math.isinf(v):
+        if v is not None and math.isinf(v):
             raise SystemExit(f"integrate: {flag} {v}: {who} integrate over a finite rectangle "
                              "(no infinite side)")
     opts = {k: v for k, v in (("rtol", a.area_rtol), ("atol", a.area_atol),
@@ -465,7 +480,12 @@ def _integrate_adaptive2d(a, lo: float, hi: float) -> int:
                               ("max_depth", a.max_depth), ("max_intervals", a.max_intervals))
             if v is not None}
     try:
-        r = integrate_expr2d_adaptive(a.expr, lo, hi, a.ya, a.yb, **opts)
+        if region:
+            from . import integrate_expr2d_region
+
+            r = integrate_expr2d_region(a.expr, lo, hi, a.y_lo, a.y_hi, **opts)
+        else:
+            r = integrate_expr2d_adaptive(a.expr, lo, hi, a.ya, a.yb, **opts)
     except (ValueError, RuntimeError) as e:
         raise SystemExit(f"integrate: {e}") from None
     if not r.converged:
@@ -681,6 +701,13 @@ def main(argv=None) -> int:
     ig.add_argument("--area-atol", type=float, default=None)
     ig.add_argument("--panels-y", type=int, default=None, help="--area-rtol / --area-atol: the "
                     "equal parts along y to start from (default: --panels)")
+    ig.add_argument("--y-lo", default=None, metavar="EXPR", help="with --y-hi and --area-rtol / "
+                    "--area-atol, in place of --ya / --yb: the double integral over a <= x <= b, "
+                    "y_lo(x) <= y <= y_hi(x), both limits expressions over x alone (write "
+                    "--y-lo=-sqrt(1.0-x*x) where one begins with a minus). The region is mapped onto "
+                    "[a, b] x [0, 1] and the rounds run on f (y_hi - y_lo); where y_hi < y_lo the "
+                    "strip counts negatively. --json also carries y_lo, y_hi")
+    ig.add_argument("--y-hi", default=None, metavar="EXPR")
     ig.add_argument("--row-rtol", type=float, default=None, help="with --expr and --params / "
                     "--linspace: every row to its own tolerance max(row-atol, row-rtol |value of "
                     "the row|), the rows sharing the rounds (one GPU, one rank); --panels and "

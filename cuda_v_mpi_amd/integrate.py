@@ -682,6 +682,66 @@ def integrate_expr2d_adaptive(expr: str, ax: float, bx: float, ay: float, by: fl
 
 
 @dataclasses.dataclass
+class AdaptiveRegionResult(Adaptive2DResult):
+    """An ``Adaptive2DResult`` of the mapped integrand f (y_hi - y_lo) on [ax, bx] x [0, 1]:
+    ``ay`` and ``by`` are 0.0 and 1.0, the ends of the mapped variable."""
+    y_lo: str               # the limits in y, expressions over x
+    y_hi: str
+
+
+def integrate_expr2d_region(expr: str, ax: float, bx: float, y_lo: str, y_hi: str,
+                            rtol: float = 1e-10, atol: float = 0.0, panels_x: int = 64,
+                            panels_y: int = 64, max_depth: int = 60,
+                            max_intervals: int = 1 << 22,
+                            backend: str = "hip") -> AdaptiveRegionResult:
+    """The double integral of f(x, y) over the region { ax <= x <= bx, y_lo(x) <= y <= y_hi(x) }
+    to the tolerance max(atol, rtol * |value|): ``expr`` over ``x`` and ``y``, the two limits
+    C++ expressions over ``x`` alone. The region is mapped onto [ax, bx] x [0, 1] by
+    y = y_lo + (y_hi - y_lo) v, and the rounds of ``integrate_expr2d_adaptive`` run on the mapped
+    integrand f (y_hi - y_lo): ``err_est``, ``resabs`` and ``tol`` are its, and ``panels_y``
+    divides v. ``ax > bx`` negates, and where y_hi(x) < y_lo(x) that strip counts negatively
+    (neither refused nor clamped). A limit that is not finite at a node makes its rectangle
+    ``nonfinite``.
+    ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr2d_region``),
+    one GPU. ``backend="cpu"``: the numpy model (``utils.adaptive_quad2d.region_model``) on
+    ``expr_torch``'s evaluation of the three expressions; needs no GPU.
+    Left out: limits in x that depend on y (swap the names), infinite sides, parameter rows,
+    more than one rank, the host engine."""
+    ax, bx = float(ax), float(bx)
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr2d_region(expr, ax, bx, y_lo, y_hi, rtol=rtol, atol=atol,
+                                       panels=(int(panels_x), int(panels_y)),
+                                       max_depth=max_depth, max_intervals=max_intervals)
+        fields = {k: getattr(r, k) for k in _ADAPT2D_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        from ._native import native
+        from .utils.adaptive_quad2d import region_model
+
+        native().expr_region_source(expr, y_lo, y_hi)   # the refusals of the hip backend
+
+        def f(x, y):
+            return expr_torch(expr, torch.from_numpy(np.ascontiguousarray(x)),
+                              torch.from_numpy(np.ascontiguousarray(y))).numpy()
+
+        def limit(which):
+            return lambda x: expr_torch(which, torch.from_numpy(np.ascontiguousarray(x))).numpy()
+
+        t0 = time.perf_counter()
+        r = region_model(f, limit(y_lo), limit(y_hi), ax, bx, rtol=rtol, atol=atol,
+                         panels_x=int(panels_x), panels_y=int(panels_y),
+                         max_depth=int(max_depth), max_intervals=int(max_intervals))
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in _ADAPT2D_FIELDS}
+    else:
+        raise ValueError("integrate_expr2d_region backend must be 'hip' or 'cpu'")
+    return AdaptiveRegionResult(**fields, device_ms=ms, expr=expr, ax=ax, bx=bx, ay=0.0, by=1.0,
+                                backend=backend, y_lo=y_lo, y_hi=y_hi)
+
+
+@dataclasses.dataclass
 class AdaptiveSweepResult:
     """Per row (numpy arrays of K entries, fields as in ``AdaptiveResult``), then the call."""
     value: "np.ndarray"

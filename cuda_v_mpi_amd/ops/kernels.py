@@ -554,6 +554,42 @@ def quad_expr2d(expr: str, ax: float, bx: float, ay: float, by: float, rtol: flo
     return r, rects[:r.intervals]
 
 
+_EXPR_REGION_CACHE: dict = {}
+
+
+def quad_expr2d_region(expr: str, ax: float, bx: float, y_lo: str, y_hi: str,
+                       rtol: float = 1e-10, atol: float = 0.0, panels=64, max_depth: int = 60,
+                       max_intervals: int = 1 << 22, return_rects: bool = False):
+    """The double integral of f(x, y) over the region { ax <= x <= bx, y_lo(x) <= y <= y_hi(x) }
+    to the tolerance max(atol, rtol * |value|): ``expr`` is one C++ expression over ``x`` and
+    ``y``, ``y_lo`` and ``y_hi`` are C++ expressions over ``x`` alone. The region is mapped onto
+    [ax, bx] x [0, 1] by y = y_lo + (y_hi - y_lo) v and ``quad_expr2d``'s rounds run on the
+    mapped integrand f (y_hi - y_lo), the evaluation kernel replaced by its twin
+    (csrc/runtime/expr_adaptive_region.cpp); the options are ``quad_expr2d``'s. Where
+    y_hi(x) < y_lo(x) that strip counts negatively. One hipRTC compile and one module per
+    (expr, y_lo, y_hi, device), cached. Returns the native Adapt2DResult; err_est, resabs and tol
+    are those of the mapped integrand. With ``return_rects`` also the final partition as an fp64
+    device tensor [n, 4] of (x0, x1, v0, v1) in the mapped variables, ordered by (v0, x0)
+    (``utils.adaptive_quad2d.region_corners`` turns them into y)."""
+    m = native()
+    px, py = (panels, panels) if isinstance(panels, int) else panels
+    opt = m.Adapt2DOptions(float(rtol), float(atol), int(px), int(py), int(max_depth),
+                           int(max_intervals))
+    m.adapt2d_check(float(ax), float(bx), 0.0, 1.0, opt)  # before any device call
+    m.expr_region_source(expr, y_lo, y_hi)                # a refused expression too
+    dev = _device()
+    key = (expr, y_lo, y_hi, dev.index)
+    ea = _EXPR_REGION_CACHE.get(key)
+    if ea is None:
+        ea = _EXPR_REGION_CACHE[key] = m.ExprAdaptiveRegion(expr, y_lo, y_hi, dev.index)
+    if not return_rects:
+        return ea.integrate(float(ax), float(bx), opt)
+    rects = torch.empty((int(max_intervals), 4), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the rounds run on their own stream
+    r = ea.integrate(float(ax), float(bx), opt, rects.data_ptr(), int(max_intervals))
+    return r, rects[:r.intervals]
+
+
 _EXPR_ADAPT_SWEEP_CACHE: dict = {}
 
 

@@ -13,6 +13,15 @@ way.
 
     r = adaptive2d_model(lambda x, y: 1.0 / np.sqrt(x * x + y * y), 0, 1, 0, 1, rtol=1e-8)
     r["value"], r["err_est"], r["converged"], r["splits_x"], r["splits_y"], r["rects"]
+
+The rule takes its 225 values a rectangle from a callback (``product_rule``) and the rounds take
+the rule as one (``rounds_model``), so the region between two curves (ExprAdaptiveRegion,
+csrc/runtime/expr_adaptive_region.cpp) is the same model around other values: ``region_model``
+maps y = g(x) + (h(x) - g(x)) v and shares the map's roundings with the kernel (the
+subtraction, the fma, the product by h - g).
+
+    r = region_model(lambda x, y: 1.0 + 0.0 * x, lambda x: -np.sqrt(1.0 - x * x),
+                     lambda x: np.sqrt(1.0 - x * x), -1, 1)      # the unit disc's area
 """
 from __future__ import annotations
 
@@ -56,6 +65,18 @@ def gk15x15(f, x0: np.ndarray, x1: np.ndarray, y0: np.ndarray, y1: np.ndarray):
     """K, err, ex, ey and R of every rectangle [x0_i, x1_i] x [y0_i, y1_i]: the rows' sums along
     x and then the rows themselves from the centre outwards, pair by pair, as the kernels add
     them. ``f(x, y)`` takes two arrays of one shape."""
+    def values(x, y):
+        xx = np.broadcast_to(x[:, None, :], (x.shape[0], 15, 15))   # [rect, row j, column i]
+        yy = np.broadcast_to(y[:, :, None], (x.shape[0], 15, 15))
+        return np.asarray(f(xx, yy), dtype=np.float64) + np.zeros(xx.shape)
+
+    return product_rule(values, x0, x1, y0, y1)
+
+
+def product_rule(values, x0: np.ndarray, x1: np.ndarray, y0: np.ndarray, y1: np.ndarray):
+    """The rule of ``gk15x15`` on 225 values a rectangle that a callback supplies:
+    ``values(x, y)`` takes the nodes of both axes (n x 15 each, ascending) and returns the
+    n x 15 x 15 values summed, [rectangle, row j, column i]."""
     from .._native import native
 
     m = native()
@@ -63,10 +84,8 @@ def gk15x15(f, x0: np.ndarray, x1: np.ndarray, y0: np.ndarray, y1: np.ndarray):
     x = m.gk15_abscissae(x0, x1)            # n x 15, ascending
     y = m.gk15_abscissae(y0, y1)
     hx, hy = 0.5 * (x1 - x0), 0.5 * (y1 - y0)
-    xx = np.broadcast_to(x[:, None, :], (x.shape[0], 15, 15))   # [rect, row j, column i]
-    yy = np.broadcast_to(y[:, :, None], (x.shape[0], 15, 15))
-    fx = np.asarray(f(xx, yy), dtype=np.float64) + np.zeros(xx.shape)
-    assert t[7] == 0.0 and fx.shape == xx.shape
+    fx = values(x, y)
+    assert t[7] == 0.0 and fx.shape == (x.shape[0], 15, 15)
     fa = np.abs(fx)
     # the row sums, every row at once: the centre column, then the pairs of columns outwards
     rk = wk[7] * fx[:, :, 7]
@@ -113,6 +132,14 @@ def adaptive2d_model(f, ax: float, bx: float, ay: float, by: float, rtol: float 
     maps two fp64 arrays of one shape to an fp64 array. Returns the fields of Adapt2DResult
     (``device_ms`` aside), ``peak`` (the longest active list) and the final partition ``rects``,
     an n x 4 array of (x0, x1, y0, y1) ordered by (y0, x0)."""
+    return rounds_model(lambda *rects: gk15x15(f, *rects), ax, bx, ay, by, rtol, atol, panels_x,
+                        panels_y, max_depth, max_intervals)
+
+
+def rounds_model(rule, ax: float, bx: float, ay: float, by: float, rtol: float, atol: float,
+                 panels_x: int, panels_y: int, max_depth: int, max_intervals: int) -> dict:
+    """The rounds of ``adaptive2d_model`` around any rule: ``rule(x0, x1, y0, y1)`` returns K,
+    err, ex, ey and R of every rectangle of a list."""
     ax, bx, ay, by = float(ax), float(bx), float(ay), float(by)
     panels_x, panels_y = int(panels_x), int(panels_y)
     check_options(ax, bx, ay, by, rtol, atol, panels_x, panels_y, max_depth, max_intervals)
@@ -136,7 +163,7 @@ def adaptive2d_model(f, ax: float, bx: float, ay: float, by: float, rtol: float 
             out["rounds"] += 1
             out["evals"] += 225 * n
             out["peak"] = max(out["peak"], n)
-            k, err, ex, ey, r = gk15x15(f, x0, x1, y0, y1)
+            k, err, ex, ey, r = rule(x0, x1, y0, y1)
             t = rtol * abs(s_acc + float(k.sum()))
             tol = float(atol) if atol > t else t          # a NaN sum: a NaN tolerance
             wx, wy = x1 - x0, y1 - y0
@@ -187,3 +214,51 @@ def adaptive2d_model(f, ax: float, bx: float, ay: float, by: float, rtol: float 
                rects=rects)
     out["converged"] = bool(e_acc <= tol and not out["capped"] and out["nonfinite"] == 0)
     return out
+
+
+def region_values(f, g, h):
+    """The 225 values a rectangle of (x, v) of the region rule (miint/expr.hpp,
+    ExprAdaptiveRegion), as a callback for ``product_rule``: per x node g_i = g(x_i) and
+    w_i = h(x_i) - g_i, per node pair y_ij = fma(w_i, v_j, g_i) and f(x_i, y_ij) * w_i, each
+    rounded as the kernel rounds it."""
+    from .._native import native
+
+    def values(x, v):
+        gx = np.asarray(g(x), dtype=np.float64) + np.zeros(x.shape)
+        w = (np.asarray(h(x), dtype=np.float64) + np.zeros(x.shape)) - gx
+        shape = (x.shape[0], 15, 15)                                  # [rect, row j, column i]
+        xx = np.broadcast_to(x[:, None, :], shape)
+        ww = np.broadcast_to(w[:, None, :], shape)
+        yy = native().fma(ww, np.broadcast_to(v[:, :, None], shape),
+                          np.broadcast_to(gx[:, None, :], shape))
+        return (np.asarray(f(xx, yy), dtype=np.float64) + np.zeros(shape)) * ww
+
+    return values
+
+
+def region_model(f, g, h, ax: float, bx: float, rtol: float = 1e-10, atol: float = 0.0,
+                 panels_x: int = 64, panels_y: int = 64, max_depth: int = 60,
+                 max_intervals: int = 1 << 22) -> dict:
+    """The integral of f(x, y) over { ax <= x <= bx, g(x) <= y <= h(x) } by the rounds of
+    ExprAdaptiveRegion: ``adaptive2d_model``'s on [ax, bx] x [0, 1] in (x, v), the 225 values of
+    a rectangle from ``region_values``. ``g`` and ``h`` map an fp64 array to one of its shape.
+    The fields are those of ``adaptive2d_model``; ``rects`` holds (x0, x1, v0, v1) ordered by
+    (v0, x0), and err_est, resabs and tol are those of the mapped integrand f (h - g). Where
+    h < g the strip counts negatively."""
+    values = region_values(f, g, h)
+    return rounds_model(lambda *rects: product_rule(values, *rects), ax, bx, 0.0, 1.0, rtol, atol,
+                        panels_x, panels_y, max_depth, max_intervals)
+
+
+def region_corners(rects: np.ndarray, g, h) -> np.ndarray:
+    """The corners in (x, y) of rectangles (x0, x1, v0, v1) of a region's partition: an
+    n x 4 x 2 array of (x, y) at (x0, v0), (x1, v0), (x1, v1), (x0, v1), where
+    y = g(x) + (h(x) - g(x)) v as the kernels form it."""
+    from .._native import native
+
+    rects = np.asarray(rects, dtype=np.float64).reshape(-1, 4)
+    x = rects[:, [0, 1, 1, 0]]
+    v = rects[:, [2, 2, 3, 3]]
+    gx = np.asarray(g(x), dtype=np.float64) + np.zeros(x.shape)
+    w = (np.asarray(h(x), dtype=np.float64) + np.zeros(x.shape)) - gx
+    return np.stack([x, native().fma(w, v, gx)], axis=2)
