@@ -38,6 +38,9 @@
 // One GPU, one rank: no sample count, rule, sweep, curve, y range or host engine goes with it.
 // With a tolerance, --a and --b also take inf, +inf, -inf and infinity (miint/expr.hpp, AdaptRange);
 // without one an infinite end is refused.
+// With --osc cos|sin --omega W beside --rtol / --atol the expression is integrated against
+// cos(W x) or sin(W x) at a cost that does not grow with W (ExprAdaptiveOsc), --b inf being the
+// Fourier tail.
 // With --params / --linspace and --row-rtol R and / or --row-atol T every row is integrated to
 // its own tolerance in shared rounds (ExprAdaptiveSweep): one line per row, or with --json the
 // per-row arrays and the call's fields; one warning with the number of rows not converged.
@@ -557,6 +560,105 @@ int run_expr_adaptive(const cli::Args& a, const RiemannConfig& cfg) {
   return 0;
 }
 
+// --expr with --osc cos|sin --omega W and --rtol / --atol: the integral of f(x) cos(W x) or
+// f(x) sin(W x) to a tolerance (ExprAdaptiveOsc); --b inf is the Fourier tail. One GPU, one rank.
+// Every conflict is refused, named, before any device call.
+bool osc_requested(const cli::Args& a) {
+  return a.has("osc") || a.has("omega") || a.has("max-cycles");
+}
+
+int run_expr_osc(const cli::Args& a, const RiemannConfig& cfg) {
+  const std::string who = "--osc / --omega";
+  MIINT_CHECK(a.has("osc"), std::string(a.has("omega") ? "--omega" : "--max-cycles") +
+                                " belongs to --osc cos|sin (the weight of an oscillatory "
+                                "integral): --osc is missing");
+  MIINT_CHECK(a.has("omega"), "--osc needs --omega W (the weight is cos(W x) or sin(W x)): "
+                              "--omega is missing");
+  MIINT_CHECK(a.has("expr"), who + " are the weight of an --expr integrand: --expr is missing");
+  MIINT_CHECK(adaptive_requested(a), who + " integrate to a tolerance: they need --rtol R / "
+                                           "--atol T");
+  for (const char* k : {"n", "rule", "running", "every", "running-out", "ya", "yb", "ny", "y-lo",
+                        "y-hi", "box", "params", "linspace", "row-rtol", "row-atol", "area-rtol",
+                        "area-atol", "panels-y", "max-total", "m", "shifts", "seed", "z",
+                        "periodic", "m-max", "loopback"})
+    MIINT_CHECK(!a.has(k), who + " integrate one f(x) against one weight to a tolerance: --" + k +
+                               " does not go with them");
+  MIINT_CHECK(a.integer("gpus", 1) <= 1, who + " run on one GPU: --gpus " + a.str("gpus", "") +
+                                             " does not go with them");
+  MIINT_CHECK(cli::env_int("WORLD_SIZE", 1) <= 1,
+              who + " run as one rank: a rank environment (WORLD_SIZE = " +
+                  std::to_string(cli::env_int("WORLD_SIZE", 1)) + ") does not go with them");
+  MIINT_CHECK(!cli::on_cpu(a), who + " have no host engine: --device cpu does not go with them");
+  MIINT_CHECK(!(std::isinf(cfg.a) || (std::isinf(cfg.b) && cfg.b < 0.0)),
+              who + " take a finite range or (A, inf): --a " + a.str("a", "") + " --b " +
+                  a.str("b", "") + " does not go with them ((-inf, b) and two-sided Fourier "
+                  "integrals are not supported)");
+  const bool tail = std::isinf(cfg.b);
+  MIINT_CHECK(tail || !a.has("max-cycles"),
+              "--max-cycles bounds the Fourier tail: it needs --b inf");
+  MIINT_CHECK(!tail || a.has("atol"),
+              "the Fourier tail (--b inf) needs --atol T: its cycles are held to shares of an "
+              "absolute tolerance, --rtol alone is refused");
+  const OscKind kind = osc_kind(a.str("osc", ""));
+  const double omega = adaptive_number(a, "omega", 0.0, false);
+  AdaptOptions o;
+  OscTailOptions t;
+  o.rtol = adaptive_number(a, "rtol", tail ? 0.0 : o.rtol, false);
+  o.atol = adaptive_number(a, "atol", 0.0, false);
+  const double panels = adaptive_number(
+      a, "panels", static_cast<double>(tail ? t.panels : o.panels), true);
+  const double depth = adaptive_number(a, "max-depth", o.max_depth, true);
+  const double max_iv = adaptive_number(a, "max-intervals", static_cast<double>(o.max_intervals), true);
+  const double cycles = adaptive_number(a, "max-cycles", t.max_cycles, true);
+  MIINT_CHECK(panels >= 0 && max_iv >= 0 && std::fabs(depth) < 1e9 && std::fabs(cycles) < 1e9,
+              "--panels, --max-intervals, --max-depth and --max-cycles must not be negative or "
+              "huge");
+  (tail ? t.panels : o.panels) = static_cast<uint64_t>(panels);
+  o.max_depth = static_cast<int>(depth);
+  o.max_intervals = static_cast<uint64_t>(max_iv);
+  t.max_cycles = static_cast<int>(cycles);
+  osc_check(cfg.a, cfg.b, omega, o, tail, t);
+  const std::string expr = a.str("expr", "");
+  (void)expr_osc_source(expr);  // a rejected expression: before any device call
+  MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprAdaptiveOsc eo(expr, 0);
+  const OscResult r = tail ? eo.integrate_tail(cfg.a, omega, kind, o, t)
+                           : eo.integrate(cfg.a, cfg.b, omega, kind, o);
+  const double secs = wall_seconds() - process_start_seconds();
+  if (!r.converged)
+    std::fprintf(stderr, "riemann: not converged: err_est %.3g against tol %.3g: %s\n", r.err_est,
+                 r.tol, r.reason.c_str());
+  if (!a.flag("json")) std::printf("%.17g\n", r.value);
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
+      .add("omega", omega).add("kind", r.kind)
+      .add("rtol", o.rtol).add("atol", o.atol)
+      .add("panels", static_cast<double>(tail ? t.panels : o.panels))
+      .add("max_depth", o.max_depth).add("max_intervals", static_cast<double>(o.max_intervals))
+      .add("value", r.value).add("err_est", r.err_est).add("resabs", r.resabs).add("tol", r.tol)
+      .add("converged", r.converged).add("evals", static_cast<double>(r.evals))
+      .add("rounds", static_cast<double>(r.rounds))
+      .add("intervals", static_cast<double>(r.intervals))
+      .add("splits", static_cast<double>(r.splits)).add("floor", static_cast<double>(r.floor))
+      .add("forced", static_cast<double>(r.forced))
+      .add("nonfinite", static_cast<double>(r.nonfinite)).add("capped", r.capped)
+      .add("range", r.range).add("cycles", static_cast<double>(r.cycles))
+      .add("extrapolated", r.extrapolated).add("reason", r.reason);
+  if (tail) rec.add("max_cycles", t.max_cycles);
+  char bits[24];
+  uint64_t w = 0;
+  std::memcpy(&w, &r.value, sizeof w);
+  std::snprintf(bits, sizeof bits, "%016llx", static_cast<unsigned long long>(w));
+  rec.add("value_bits", bits);
+  if (a.has("analytic")) {
+    const double exact = a.num("analytic", 0.0);
+    rec.add("analytic", exact).add("abs_err", std::fabs(r.value - exact));
+  }
+  cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
+  return 0;
+}
+
 // --expr with --ya / --yb and --area-rtol / --area-atol: the double integral to a tolerance
 // (ExprAdaptive2D). One GPU, one rank. Refusals come before any device call.
 bool area_adaptive_requested(const cli::Args& a) {
@@ -987,6 +1089,8 @@ constexpr const char* kUsage =
     "                [--panels P] [--panels-y Q] [--max-depth D] [--max-intervals M]]\n"
     "               [--expr EXPR --a A --b B --rtol R [--atol T] [--panels P] [--max-depth D]\n"
     "                [--max-intervals M]]\n"
+    "               [--expr EXPR --a A --b B|inf --osc cos|sin --omega W --rtol R [--atol T]\n"
+    "                [--panels P] [--max-depth D] [--max-intervals M] [--max-cycles C]]\n"
     "               [--expr EXPR --a A --b B --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
     "                [--row-atol T] [--panels P] [--max-depth D] [--max-intervals M] [--max-total N]]\n"
     "               [--expr EXPR --box A0:B0,A1:B1,... --m M | --rtol R [--atol T] [--m-max M]\n"
@@ -1036,6 +1140,16 @@ constexpr const char* kUsage =
     "  finite end (exp(-x)/sqrt(x) on (0, inf)) ends as nonfinite: split it at 1; an oscillatory\n"
     "  tail (sin(x)/x) does not converge, and the run says so. The same holds with --row-rtol.\n"
     "  An infinite A or B without --rtol / --atol / --row-rtol / --row-atol is refused.\n"
+    "--osc cos|sin --omega W: with --rtol R / --atol T, the integral of --expr times cos(W x) or\n"
+    "  sin(W x) on [A, B] to the tolerance, at a cost that does not grow with W: adaptive\n"
+    "  Filon-Clenshaw-Curtis (13, 25), 25 evaluations an interval, the weight integrated exactly;\n"
+    "  --panels, --max-depth and --max-intervals as for --rtol. f must be finite on the closed\n"
+    "  range (both ends of every interval are evaluated). --b inf is the Fourier tail on (A, inf):\n"
+    "  W != 0 and --atol are required (--rtol alone is refused), --panels is per cycle (default\n"
+    "  16), --max-cycles C bounds it (default 50). --json adds omega, kind, cycles, extrapolated,\n"
+    "  reason. Refused, naming the conflict: --osc without --omega and the reverse, no tolerance,\n"
+    "  --n, --rule, --running, --ya, --y-lo, --box, --params, --linspace, --row-rtol, --area-rtol,\n"
+    "  --gpus above 1, --loopback, WORLD_SIZE above 1, --device cpu, --a -inf.\n"
     "--row-rtol R / --row-atol T: with --params or --linspace, the integral of --expr on [A, B] for\n"
     "  every row to the row's own tolerance max(T, R |value of the row|), the rows sharing the\n"
     "  rounds (--panels P per row, default: 65536 / rows as a power of two, at least 16;\n"
@@ -1100,6 +1214,7 @@ int main(int argc, char** argv) {
     if (f == Integrand::kTable) cfg.table = prof;
     if (f == Integrand::kPoly) cfg.coef = {1.0, -0.5, 0.25, 0.125};
 
+    if (osc_requested(a)) return run_expr_osc(a, cfg);  // it names its own conflicts
     MIINT_CHECK(a.has("expr") || !(a.has("params") || a.has("linspace")),
                 "--params / --linspace sweep the parameters of an --expr integrand");
     MIINT_CHECK(a.has("expr") || !a.has("running"),

@@ -507,10 +507,20 @@ class ExprAdaptive {
   const std::string& expression() const { return expr_; }
 
  private:
+  friend class ExprAdaptiveOsc;  // the same rounds and buffers around another evaluation kernel
+  // An evaluation kernel from another module in place of miint_adapt_eval: `launch` enqueues it
+  // on the rounds' stream for the n intervals of `list` and their depths, storing K, err, R and
+  // the workgroups' partials of K as miint_adapt_eval does; evals_per counts f per interval.
+  struct EvalTwin {
+    std::function<void(unsigned blocks, unsigned long long n, const double* list,
+                       const unsigned* depth)> launch;
+    uint64_t evals_per = 15;
+  };
   void reserve(uint64_t max_intervals);
   // kind kFinite: f on [lo, hi]; else g of that kind and `end` on [lo, hi] = [0, 1].
   AdaptResult rounds(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t cap,
-                     AdaptRange kind = AdaptRange::kFinite, double end = 0.0);
+                     AdaptRange kind = AdaptRange::kFinite, double end = 0.0,
+                     const EvalTwin* twin = nullptr);
   void load_unbounded();
   std::string expr_;
   int device_;
@@ -527,6 +537,151 @@ class ExprAdaptive {
   Event e0_, e1_;
   detail::RtcModule module_;  // the last members: destroyed first (miint/expr_rtc.hpp)
   std::unique_ptr<detail::RtcModule> unbounded_;  // loaded at the first unbounded call
+};
+
+// ---------------------------------------------------------------------------------------
+// Oscillatory weights: the integral of f(x) cos(omega x) or f(x) sin(omega x) on [a, b] to a
+// requested tolerance, omega a number of the call and not part of f (QUADPACK's qawo), and the
+// Fourier tail on (a, +inf) (its qawf). ExprAdaptive pays for an oscillatory factor in
+// bisections: |K15 - G7| means nothing until an interval is shorter than a period. Here the
+// rule is Filon-Clenshaw-Curtis: the weight is integrated exactly and only f is interpolated,
+// so one interval may hold any number of periods (expr_adaptive_osc.cpp).
+//
+// On [lo, hi] with hw = 0.5 (hi - lo), c = lo + hw, the 25 Chebyshev extrema t_j = cos(j pi /
+// 24), j = 0 (t = 1, the upper end) .. 24 (t = -1), the nodes x_j = fma(hw, t_j, c) and x_{24-j}
+// = fma(hw, -t_j, c); the 13 even-numbered ones are the embedded coarse rule. Both ends are
+// nodes. With l_j the Lagrange basis on the 25 (or the 13) nodes and par = omega hw:
+//   Wc_j(par) = int_{-1}^{1} l_j(t) cos(par t) dt,   Ws_j(par) = int l_j(t) sin(par t) dt,
+// Wc_{24-j} = Wc_j and Ws_{24-j} = -Ws_j (Ws_12 = 0), so the kernel works on mirrored pairs and
+// half tables. Operation by operation, contraction off (miint_osc_rule):
+//   f12 = f(c); for j = 11 down to 0: fp = f(fma(hw, t_j, c)), fm = f(fma(hw, -t_j, c)),
+//     s = fp + fm, d = fp - fm, a = |fp| + |fm|
+//   ic24 = Wc24_12 f12, then ic24 = fma(Wc24_j, s, ic24);  is24 = Ws24_11 d (at j = 11), then
+//     is24 = fma(Ws24_j, d, is24);  ic12, is12 the same over the even j with Wc12, Ws12 (is12
+//     starts at j = 10);  sa = w_12 |f12|, then sa = fma(w_j, a, sa), w the plain 25-point
+//     Clenshaw-Curtis weights
+//   p = omega c, e = fma(omega, c, -p) (the product's rounding error, exact), (S0, C0) =
+//     sincos(p), S = fma(e, C0, S0), C = fma(-e, S0, C0): the phase omega c to about an ulp of S
+//     and C, not to an ulp of p
+//   cos: K = hw (C ic24 - S is24), G = hw (C ic12 - S is12)
+//   sin: K = hw (S ic24 + C is24), G = hw (S ic12 + C is12)
+//   err = |K - G|, R = hw sa: the rule's integral of |f| (it bounds that of |f w|) and feeds the
+//   floor test unchanged.
+// omega = 0 gives e = 0, S = 0, C = 1 exactly: plain Clenshaw-Curtis (25, 13) for cos, 0 for sin.
+//
+// The weights depend on par only, and the intervals of one depth share it. The nominal value
+// is par_d = omega hw0 2^-d with hw0 = 0.5 ((b - a) / panels), halved exactly; the host builds
+// one table per call, a row of kOscRow doubles per depth 0 .. max_depth (Wc24[13], Ws24[12],
+// Wc12[7], Ws12[6], two of padding), uploads it, and the kernel indexes it by the interval's
+// depth: no recurrence and no branch on par in the kernel, one path for every omega, 25
+// evaluations, four dot products and one sincos a lane.
+//
+// osc_weights(par) on the host, in long double (64-bit significand), from the Chebyshev moments
+// M_k = int T_k(t) exp(i par t) dt, k = 0 .. 24 (real for even k, imaginary for odd k):
+//   |par| < 64: exp(i par t) = J_0 + 2 sum_n i^n J_n(par) T_n(t), J_n by Miller's backward
+//     recurrence from n = 2 ceil(|par| / 2) + 96, normalised with J_0 + 2 sum J_2m = 1, and
+//     int T_k T_n = 1 / (1 - (k + n)^2) + 1 / (1 - (k - n)^2) for k + n even, else 0. Every term
+//     is bounded, and J_n has dropped far below 2^-64 where the series is cut.
+//   |par| >= 64: by parts, M_k = (B_k - D_k) / (i par) with B_k = exp(i par) - (-1)^k exp(-i
+//     par) and D_k = int T_k' exp(i par t) dt, D_1 = M_0 = 2 sin(par) / par, D_2 = 4 M_1,
+//     D_{k+1} = (k + 1) (2 M_k + D_{k-1} / (k - 1)), forwards. An error in D_k is passed on times
+//     2 (k + 1) / |par| < 1 for k <= 24: stable.
+//   par = 0: M_k = 2 / (1 - k^2), k even.
+// Then W_j = (2 / N) c_j sum''_k cos(j k pi / N) M_k (c_j = 1/2 at the ends, the first and last
+// term of the sum halved), N = 24 and 12, rounded to double. Wc is even and Ws odd in par.
+// tests/test_expr_osc_cpu.py holds them to 50-digit values.
+//
+// Limits. Both ends of every interval are evaluated, so f must be finite on the closed range:
+// an end singularity (1.0/sqrt(x) from 0) reports `nonfinite`, and the "singular end" advice of
+// the Gauss-Kronrod rule does not carry over. The intervals' widths differ from the nominal
+// hw0 2^-d by the rounding of their ends, about 2^-53 max|x|, so par is off by |omega| times
+// that, and the nodes' rounding moves the weight's phase by as much: the value is uncertain by
+// about |omega| max|x| 2^-53 relative to the intervals' own contributions, whatever the
+// tolerance asked. omega and the ends must be finite; a > b negates; a == b gives 0 with no
+// launch.
+//
+// The Fourier tail (b = +inf, omega != 0), a host loop over the finite rule: cycles of length
+// L = (2 floor(|omega|) + 1) pi / |omega| from a, cycle k = 1, 2, ... one finite call on [a +
+// (k - 1) L, a + k L] from OscTailOptions::panels panels with rtol = 0 and atol (1 - p) p^(k -
+// 1), p = 0.9. From 3 cycles on Wynn's epsilon algorithm runs on the partial sums; the
+// extrapolation's estimate is |e_k - e_{k-1}| + |e_k - e_{k-2}| over its last three results (so
+// from cycle 5). The loop stops when (the sum of the cycles' err_est) + 50 |cycle k| <= atol
+// (the sum itself has converged: `extrapolated` false), when (that sum) + (the extrapolation's
+// estimate) <= atol (`extrapolated` true, the value is e_k), or at max_cycles. err_est is the
+// sum of the cycles' estimates plus the estimate of whichever stopped it. `converged` further
+// asks that every cycle converged and that f decays: the last cycle's R must be below the first
+// one's (f = 1.0 sums to 0 in Abel's sense; the run ends `no decay` instead). atol > 0 is
+// required.
+// ---------------------------------------------------------------------------------------
+constexpr int kOscRow = 40;  // doubles per depth: Wc24[13], Ws24[12], Wc12[7], Ws12[6], 2 unused
+enum class OscKind { kCos = 0, kSin = 1 };
+// "cos" or "sin"; osc_kind throws on any other name.
+const char* osc_kind_name(OscKind kind);
+OscKind osc_kind(const std::string& name);
+// t_j = cos(j pi / 24), j = 0 .. 24 (descending from 1 to -1), and the plain Clenshaw-Curtis
+// weights of those nodes: the doubles the generated source prints.
+std::vector<double> osc_nodes();
+std::vector<double> osc_cc_weights();
+// Wc24[25], Ws24[25], Wc12[13], Ws12[13] in that order (76 doubles), node order as osc_nodes()
+// (the 13-node rule on its even ones). Throws unless par is finite.
+std::vector<double> osc_weights(double par);
+// The row of the device table for par: the half tables, kOscRow doubles.
+void osc_table_row(double par, double* row);
+// The 25 nodes of [lo, hi] in the order of osc_nodes(): the bits the kernels evaluate f at.
+void osc_abscissae(double lo, double hi, double* x25);
+
+struct OscTailOptions {
+  uint64_t panels = 16;   // per cycle
+  int max_cycles = 50;
+};
+struct OscResult : AdaptResult {
+  double omega = 0.0;
+  std::string kind = "cos";
+  uint64_t cycles = 0;         // the Fourier tail's finite calls; 0 for a finite range
+  bool extrapolated = false;   // the value is the epsilon algorithm's
+  std::string reason;          // why a run did not converge ("" when it did)
+};
+
+// adapt_check on the ends (b = +inf is taken with `tail`), omega finite; for the tail also
+// omega != 0, a finite, atol > 0, 1 <= max_cycles <= 10000 and the cycle's panels.
+void osc_check(double a, double b, double omega, const AdaptOptions& opt, bool tail = false,
+               const OscTailOptions& topt = {});
+// The two evaluation twins, miint_osc_eval_cos and miint_osc_eval_sin (the other kernels of a
+// round are expr_adapt_source's, unchanged).
+std::string expr_osc_source(const std::string& expr);
+std::string expr_osc_compile(const std::string& expr);
+// Wynn's epsilon algorithm on the sequence s[0 .. n), n >= 3: the last entry of the highest
+// even column. Plain doubles in a fixed order (the numpy model repeats it).
+double osc_epsilon(const double* s, int n);
+// Why a finished finite run did not converge ("" when it did), from its counters.
+std::string osc_reason(const AdaptResult& r);
+
+class ExprAdaptiveOsc {
+ public:
+  ExprAdaptiveOsc(const std::string& expr, int device = 0);
+  // The integral of f(x) cos(omega x) (or sin) on [a, b] by ExprAdaptive's rounds around the
+  // rule above; intervals_out as ExprAdaptive::integrate. evals counts 25 per interval.
+  OscResult integrate(double a, double b, double omega, OscKind kind, const AdaptOptions& opt = {},
+                      double* intervals_out = nullptr, uint64_t capacity = 0);
+  // The same on (a, +inf) by the cycles above. opt.panels is not used (topt.panels is).
+  OscResult integrate_tail(double a, double omega, OscKind kind, const AdaptOptions& opt,
+                           const OscTailOptions& topt = {});
+  double time(double a, double b, double omega, OscKind kind, const AdaptOptions& opt, int iters);
+  const std::string& expression() const { return rounds_.expression(); }
+  uint64_t table_uploads() const { return uploads_; }
+
+ private:
+  void upload(double par0, int rows, int upto);
+  AdaptResult run(double lo, double hi, double hw0, double omega, OscKind kind,
+                  const AdaptOptions& opt, double* out, uint64_t cap);
+  ExprAdaptive rounds_;  // its buffers and rounds around the twins
+  DeviceBuffer<double> table_;          // (max_depth + 1) x kOscRow
+  std::vector<double> host_table_;
+  double table_par0_ = 0.0;
+  int table_rows_ = 0;                  // rows allocated
+  int table_depths_ = 0;                // rows 0 .. table_depths_ - 1 hold table_par0_'s weights
+  uint64_t uploads_ = 0;
+  detail::RtcModule twins_;  // the last member: destroyed first (miint/expr_rtc.hpp)
 };
 
 // ---------------------------------------------------------------------------------------

@@ -1121,6 +1121,132 @@ PYBIND11_MODULE(_miint, m) {
            py::arg("iters"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("expression", &ExprAdaptive::expression);
 
+  // oscillatory weights: Filon-Clenshaw-Curtis (13, 25) against cos(omega x) or sin(omega x)
+  m.attr("OSC_ROW") = kOscRow;
+  m.def("osc_nodes", [as_array] { return as_array(osc_nodes()); },
+        "the 25 Chebyshev extrema cos(j pi / 24), j = 0 .. 24, descending");
+  m.def("osc_cc_weights", [as_array] { return as_array(osc_cc_weights()); },
+        "the plain Clenshaw-Curtis weights of osc_nodes()");
+  m.def("osc_weights",
+        [as_array](double par) {
+          const std::vector<double> w = osc_weights(par);
+          auto part = [&](size_t from, size_t count) {
+            return as_array(std::vector<double>(w.begin() + from, w.begin() + from + count));
+          };
+          return py::make_tuple(part(0, 25), part(25, 25), part(50, 13), part(63, 13));
+        },
+        py::arg("par"),
+        "(Wc24, Ws24, Wc12, Ws12): the integrals of the Lagrange basis on the 25 (13) Chebyshev "
+        "extrema against cos(par t) and sin(par t) over [-1, 1], the doubles the device table holds");
+  m.def("osc_table_row",
+        [as_array](double par) {
+          std::vector<double> row(kOscRow);
+          osc_table_row(par, row.data());
+          return as_array(row);
+        },
+        py::arg("par"), "a depth's row of the device table: the half tables");
+  m.def("osc_abscissae",
+        [](py::array_t<double, py::array::c_style | py::array::forcecast> lo,
+           py::array_t<double, py::array::c_style | py::array::forcecast> hi) {
+          MIINT_CHECK(lo.ndim() == 1 && hi.ndim() == 1 && lo.shape(0) == hi.shape(0),
+                      "osc_abscissae: lo and hi are 1-D arrays of one length");
+          const py::ssize_t n = lo.shape(0);
+          py::array_t<double> out({n, py::ssize_t(25)});
+          for (py::ssize_t i = 0; i < n; ++i)
+            osc_abscissae(lo.data()[i], hi.data()[i], out.mutable_data() + 25 * i);
+          return out;
+        },
+        py::arg("lo"), py::arg("hi"),
+        "the nodes of every interval [lo_i, hi_i] as an n x 25 array in the order of osc_nodes(): "
+        "the bits the oscillatory kernels evaluate f at");
+  m.def("osc_epsilon",
+        [](py::array_t<double, py::array::c_style | py::array::forcecast> s) {
+          MIINT_CHECK(s.ndim() == 1, "osc_epsilon: s is a 1-D array");
+          return osc_epsilon(s.data(), static_cast<int>(s.shape(0)));
+        },
+        py::arg("s"), "Wynn's epsilon algorithm on the partial sums s (at least 3)");
+  py::class_<OscTailOptions>(m, "OscTailOptions", "the Fourier tail's cycles")
+      .def(py::init([](uint64_t panels, int max_cycles) {
+             OscTailOptions o;
+             o.panels = panels;
+             o.max_cycles = max_cycles;
+             return o;
+           }),
+           py::arg("panels") = 16, py::arg("max_cycles") = 50)
+      .def_readwrite("panels", &OscTailOptions::panels)
+      .def_readwrite("max_cycles", &OscTailOptions::max_cycles);
+  py::class_<OscResult, AdaptResult>(m, "OscResult",
+                                     "AdaptResult and omega, kind, cycles, extrapolated, reason")
+      .def_readonly("omega", &OscResult::omega)
+      .def_readonly("kind", &OscResult::kind)
+      .def_readonly("cycles", &OscResult::cycles)
+      .def_readonly("extrapolated", &OscResult::extrapolated)
+      .def_readonly("reason", &OscResult::reason)
+      .def("as_dict", [](const OscResult& r) {
+        py::dict d;
+        d["value"] = r.value;
+        d["err_est"] = r.err_est;
+        d["resabs"] = r.resabs;
+        d["tol"] = r.tol;
+        d["converged"] = r.converged;
+        d["evals"] = r.evals;
+        d["rounds"] = r.rounds;
+        d["intervals"] = r.intervals;
+        d["splits"] = r.splits;
+        d["floor"] = r.floor;
+        d["forced"] = r.forced;
+        d["nonfinite"] = r.nonfinite;
+        d["capped"] = r.capped;
+        d["device_ms"] = r.device_ms;
+        d["range"] = r.range;
+        d["omega"] = r.omega;
+        d["kind"] = r.kind;
+        d["cycles"] = r.cycles;
+        d["extrapolated"] = r.extrapolated;
+        d["reason"] = r.reason;
+        return d;
+      });
+  m.def("osc_check",
+        [](double a, double b, double omega, const AdaptOptions& o, bool tail,
+           const OscTailOptions& t) { osc_check(a, b, omega, o, tail, t); },
+        py::arg("a"), py::arg("b"), py::arg("omega"), py::arg("options"),
+        py::arg("tail") = false, py::arg("tail_options") = OscTailOptions(),
+        "raise, naming the numbers, unless ExprAdaptiveOsc takes the range, omega and options");
+  m.def("expr_osc_source", &expr_osc_source, py::arg("expr"),
+        "source of the two oscillatory eval kernels generated for an expression over x");
+  m.def("expr_osc_compile", compiled(&expr_osc_compile), py::arg("expr"),
+        "compile the oscillatory eval kernels for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprAdaptiveOsc>(m, "ExprAdaptiveOsc",
+                              "the integral of f(x) cos(omega x) or f(x) sin(omega x) to a "
+                              "requested tolerance (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("device") = 0)
+      .def("integrate",
+           [](ExprAdaptiveOsc& e, double a, double b, double omega, const std::string& kind,
+              const AdaptOptions& o, uintptr_t out, uint64_t capacity) {
+             return e.integrate(a, b, omega, osc_kind(kind), o, reinterpret_cast<double*>(out),
+                                capacity);
+           },
+           py::arg("a"), py::arg("b"), py::arg("omega"), py::arg("kind") = "cos",
+           py::arg("options") = AdaptOptions(), py::arg("intervals_out") = 0,
+           py::arg("capacity") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("integrate_tail",
+           [](ExprAdaptiveOsc& e, double a, double omega, const std::string& kind,
+              const AdaptOptions& o, const OscTailOptions& t) {
+             return e.integrate_tail(a, omega, osc_kind(kind), o, t);
+           },
+           py::arg("a"), py::arg("omega"), py::arg("kind") = "cos",
+           py::arg("options") = AdaptOptions(), py::arg("tail_options") = OscTailOptions(),
+           py::call_guard<py::gil_scoped_release>())
+      .def("time",
+           [](ExprAdaptiveOsc& e, double a, double b, double omega, const std::string& kind,
+              const AdaptOptions& o, int iters) {
+             return e.time(a, b, omega, osc_kind(kind), o, iters);
+           },
+           py::arg("a"), py::arg("b"), py::arg("omega"), py::arg("kind"), py::arg("options"),
+           py::arg("iters"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("table_uploads", &ExprAdaptiveOsc::table_uploads)
+      .def_property_readonly("expression", &ExprAdaptiveOsc::expression);
+
   // adaptive double integrals: the (7, 15) x (7, 15) product on rectangles bisected by rounds
   m.attr("ADAPT2D_DEFAULT_PANELS") = kAdapt2DDefaultPanels;
   py::class_<Adapt2DOptions>(m, "Adapt2DOptions",

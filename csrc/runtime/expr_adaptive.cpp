@@ -523,7 +523,8 @@ void ExprAdaptive::reserve(uint64_t m) {
 
 // lo < hi. `out` (or null) takes the partition in acceptance order; integrate() orders it.
 AdaptResult ExprAdaptive::rounds(double lo, double hi, const AdaptOptions& opt, double* out,
-                                 uint64_t cap, AdaptRange kind, double end) {
+                                 uint64_t cap, AdaptRange kind, double end,
+                                 const EvalTwin* twin) {
   hipStream_t s = stream_.get();
   const unsigned long long max_iv = opt.max_intervals;
   const unsigned max_depth = static_cast<unsigned>(opt.max_depth);
@@ -546,7 +547,9 @@ AdaptResult ExprAdaptive::rounds(double lo, double hi, const AdaptOptions& opt, 
     const double2* list = reinterpret_cast<const double2*>(list_[cur].get());
     double2* next = reinterpret_cast<double2*>(list_[cur ^ 1].get());
     const unsigned* depth = depth_[cur].get();
-    if (kind == AdaptRange::kFinite)
+    if (twin != nullptr)
+      twin->launch(blocks, n, list_[cur].get(), depth);
+    else if (kind == AdaptRange::kFinite)
       module_.launch(kEval, blocks, 1, kAdaptBlock, s, n, list, k_.get(), err_.get(), r_.get(),
                      part_k_.get());
     else  // the twin of the kind: kernels 0, 1, 2 of unbounded_
@@ -569,7 +572,7 @@ AdaptResult ExprAdaptive::rounds(double lo, double hi, const AdaptOptions& opt, 
                    done, done_cap);
     stream_.sync();
     ++r.rounds;
-    r.evals += 15 * n;
+    r.evals += (twin != nullptr ? twin->evals_per : 15) * n;
     if (record_[kCapped] != 0 || record_[kNext] == 0) break;
     n = record_[kNext];
     cur ^= 1;

@@ -23,7 +23,10 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     ``ops.kernels.riemann_expr2d``, ``riemann --expr ... --ya AY --yb BY``), and its
     integral to a requested tolerance with an error estimate, the samples placed where
     the integrand needs them (``integrate_expr_adaptive``, ``ops.kernels.quad_expr``,
-    ``riemann --expr ... --rtol R``), and the same for f(x, p) over K parameter rows, each
+    ``riemann --expr ... --rtol R``), and its integral against cos(omega x) or sin(omega x)
+    at a cost that does not grow with omega, the Fourier tail on (a, inf) included
+    (``integrate_expr_oscillatory``, ``ops.kernels.quad_expr_osc``,
+    ``riemann --expr ... --osc cos --omega W --rtol R``), and the same for f(x, p) over K parameter rows, each
     row to its own tolerance in shared rounds (``integrate_expr_adaptive_sweep``,
     ``ops.kernels.quad_expr_sweep``, ``riemann --expr ... --params FILE --row-rtol R``), and
     the double integral of f(x, y) over a rectangle to a tolerance
@@ -49,6 +52,7 @@ from .integrate import RunningResult, integrate_expr_running  # noqa: F401
 from .integrate import integrate_expr2d  # noqa: F401
 from .integrate import AdaptiveResult, integrate_expr_adaptive  # noqa: F401
 from .integrate import AdaptiveSweepResult, integrate_expr_adaptive_sweep  # noqa: F401
+from .integrate import OscillatoryResult, integrate_expr_oscillatory  # noqa: F401
 from .integrate import Adaptive2DResult, integrate_expr2d_adaptive  # noqa: F401
 from .integrate import AdaptiveRegionResult, integrate_expr2d_region  # noqa: F401
 from .integrate import LatticeResult, integrate_expr_nd  # noqa: F401

@@ -216,6 +216,8 @@ def _json_ends(rec: dict) -> dict:
 def cmd_integrate(a) -> int:
     from . import Integrator
 
+    if a.osc is not None or a.omega is not None or a.max_cycles is not None:
+        return _integrate_osc(a)
     for flag, v in (("--a", a.a), ("--b", a.b)):
         if (v is not None and v in (float("inf"), float("-inf"))
                 and not (a.expr and not a.box and any(t is not None for t in (
@@ -427,6 +429,83 @@ def _integrate_adaptive(a, lo: float, hi: float) -> int:
     if a.analytic is not None:
         rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
     print(json.dumps(rec))
+    return 0
+
+
+def _integrate_osc(a) -> int:
+    """integrate --expr E --osc cos|sin --omega W --rtol R / --atol T: the integral of f(x)
+    cos(W x) or f(x) sin(W x) to a tolerance (one GPU, one rank; --backend cpu: the numpy
+    model); --b inf is the Fourier tail. Whatever belongs to another mode is refused before
+    anything runs, naming the conflict."""
+    import math
+    import os
+
+    from . import integrate_expr_oscillatory
+
+    who = "--osc / --omega"
+    if a.osc is None:
+        which = "--omega" if a.omega is not None else "--max-cycles"
+        raise SystemExit(f"integrate: {which} belongs to --osc cos|sin (the weight of an "
+                         "oscillatory integral): --osc is missing")
+    if a.omega is None:
+        raise SystemExit("integrate: --osc needs --omega W (the weight is cos(W x) or sin(W x)): "
+                         "--omega is missing")
+    if not a.expr:
+        raise SystemExit(f"integrate: {who} are the weight of an --expr integrand: --expr is "
+                         "missing")
+    if a.rtol is None and a.atol is None:
+        raise SystemExit(f"integrate: {who} integrate to a tolerance: they need --rtol R / "
+                         "--atol T")
+    given = {"--n": a.n is not None, "--rule": a.rule is not None, "--ya": a.ya is not None,
+             "--yb": a.yb is not None, "--ny": a.ny is not None, "--y-lo": a.y_lo is not None,
+             "--y-hi": a.y_hi is not None, "--box": bool(a.box), "--params": bool(a.params),
+             "--linspace": bool(a.linspace), "--row-rtol": a.row_rtol is not None,
+             "--row-atol": a.row_atol is not None, "--area-rtol": a.area_rtol is not None,
+             "--area-atol": a.area_atol is not None, "--panels-y": a.panels_y is not None,
+             "--max-total": a.max_total is not None, "--m": a.m is not None,
+             "--shifts": a.shifts is not None, "--seed": a.seed is not None, "--z": bool(a.z),
+             "--periodic": a.periodic, "--m-max": a.m_max is not None}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: {who} integrate one f(x) against one weight to a "
+                             f"tolerance: {flag} does not go with them")
+    if a.device == "cpu" or a.backend == "host":
+        which = "--device cpu" if a.device == "cpu" else "--backend host"
+        raise SystemExit(f"integrate: {who} have no host engine: {which} does not go with them")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"integrate: {who} run as one rank: a rank environment "
+                         f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
+    lo = 0.0 if a.a is None else a.a
+    hi = 1.0 if a.b is None else a.b
+    if lo == -math.inf or hi == -math.inf or lo == math.inf:
+        raise SystemExit(f"integrate: {who} take a finite range or (A, inf): --a {lo:g} --b "
+                         f"{hi:g} does not go with them ((-inf, b) and two-sided Fourier "
+                         "integrals are not supported)")
+    if a.max_cycles is not None and hi != math.inf:
+        raise SystemExit("integrate: --max-cycles bounds the Fourier tail: it needs --b inf")
+    opts = {k: v for k, v in (("rtol", a.rtol), ("atol", a.atol), ("panels", a.panels),
+                              ("max_depth", a.max_depth), ("max_intervals", a.max_intervals),
+                              ("max_cycles", a.max_cycles)) if v is not None}
+    if hi == math.inf and a.panels is not None:
+        opts["tail_panels"] = opts.pop("panels")
+    if hi == math.inf and a.rtol is not None and a.atol is None:
+        raise SystemExit("integrate: the Fourier tail (--b inf) needs --atol T: its cycles are "
+                         "held to shares of an absolute tolerance, --rtol alone is refused")
+    if hi == math.inf:
+        opts.setdefault("rtol", 0.0)
+    try:
+        r = integrate_expr_oscillatory(a.expr, lo, hi, a.omega, a.osc, backend=a.backend, **opts)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    if not r.converged:
+        print(f"integrate: not converged: err_est {r.err_est:.3g} against tol {r.tol:.3g}: "
+              f"{r.reason}", file=sys.stderr)
+    rec = _json_ends(r.as_dict())
+    rec["value_bits"] = "%016x" % int.from_bytes(__import__("struct").pack("<d", r.value),
+                                                 "little")
+    if a.analytic is not None:
+        rec.update(analytic=a.analytic, abs_err=abs(r.value - a.analytic))
+    print(json.dumps(rec) if a.json else f"{r.value:.17g}")
     return 0
 
 
@@ -691,6 +770,16 @@ def main(argv=None) -> int:
                     "intervals to start from (65536)")
     ig.add_argument("--max-depth", type=int, default=None, help="bisections of one interval (60)")
     ig.add_argument("--max-intervals", type=int, default=None, help="intervals in all (2^22)")
+    ig.add_argument("--osc", default=None, choices=["cos", "sin"], help="with --expr, --omega W "
+                    "and --rtol / --atol: the integral of f(x) cos(W x) or f(x) sin(W x) to the "
+                    "tolerance, at a cost that does not grow with W (Filon-Clenshaw-Curtis (13, "
+                    "25): one GPU, one rank; --backend cpu runs the numpy model). f must be "
+                    "finite on the closed range. --b inf is the Fourier tail on (A, inf): it "
+                    "needs W != 0 and --atol, --panels is then per cycle (16) and --max-cycles "
+                    "bounds it. --json also carries omega, kind, cycles, extrapolated, reason")
+    ig.add_argument("--omega", type=float, default=None, help="--osc: the weight's frequency W")
+    ig.add_argument("--max-cycles", type=int, default=None, help="--osc with --b inf: the "
+                    "cycles of the Fourier tail (50)")
     ig.add_argument("--area-rtol", type=float, default=None, help="with --expr and --ya / --yb: "
                     "the double integral over the finite rectangle to the tolerance "
                     "max(area-atol, area-rtol |value|): the (7, 15) x (7, 15) product on rectangles "

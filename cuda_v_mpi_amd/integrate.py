@@ -606,6 +606,69 @@ def integrate_expr_adaptive(expr: str, a: float, b: float, rtol: float = 1e-10,
 
 
 @dataclasses.dataclass
+class OscillatoryResult(AdaptiveResult):
+    """``AdaptiveResult`` (evals counts 25 per interval; err_est sums |K25 - K13|) and the
+    weight: cos(omega x) or sin(omega x). ``cycles`` and ``extrapolated`` describe a Fourier
+    tail (b = inf); ``reason`` says why a run did not converge."""
+    omega: float = 0.0
+    kind: str = "cos"
+    cycles: int = 0
+    extrapolated: bool = False
+    reason: str = ""
+
+
+_OSC_FIELDS = _ADAPT_FIELDS + ("omega", "kind", "cycles", "extrapolated", "reason")
+
+
+def integrate_expr_oscillatory(expr: str, a: float, b: float, omega: float, kind: str = "cos",
+                               rtol: float = 1e-10, atol: float = 0.0, panels: int = 65536,
+                               max_depth: int = 60, max_intervals: int = 1 << 22,
+                               tail_panels: int = 16, max_cycles: int = 50,
+                               backend: str = "hip") -> OscillatoryResult:
+    """The integral of f(x) cos(omega x) or f(x) sin(omega x) on [a, b] to the tolerance
+    max(atol, rtol * |value|): f is one C++ expression over ``x``, omega a number, and the cost
+    does not grow with omega (adaptive Filon-Clenshaw-Curtis: the weight is integrated exactly,
+    only f is interpolated). ``backend="hip"``: the hipRTC-compiled gfx950 kernels
+    (``ops.kernels.quad_expr_osc``), one GPU. ``backend="cpu"``: the numpy model of the same
+    rule (``utils.adaptive_osc``) on ``expr_torch``'s evaluation of the expression; needs no
+    GPU. f must be finite on the closed range: both ends of every interval are evaluated.
+    ``b = inf`` is the Fourier tail on (a, inf): it needs omega != 0 and atol > 0 (rtol alone is
+    refused), runs cycles of ``tail_panels`` panels and extrapolates their partial sums; a = -inf
+    is not supported. One rank, one f(x), one omega."""
+    import math
+
+    a, b, omega = float(a), float(b), float(omega)
+    tail = math.isinf(b) and b > 0 and math.isfinite(a)
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr_osc(expr, a, b, omega, kind, rtol=rtol, atol=atol, panels=panels,
+                                  max_depth=max_depth, max_intervals=max_intervals,
+                                  tail_panels=tail_panels, max_cycles=max_cycles)
+        fields = {k: getattr(r, k) for k in _OSC_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        from .utils.adaptive_osc import osc_model, osc_tail_model
+
+        def f(x):
+            return expr_torch(expr, torch.from_numpy(np.ascontiguousarray(x))).numpy()
+
+        t0 = time.perf_counter()
+        if tail:
+            r = osc_tail_model(f, a, omega, kind, atol=atol, rtol=rtol, max_depth=int(max_depth),
+                               max_intervals=int(max_intervals), panels=int(tail_panels),
+                               max_cycles=int(max_cycles))
+        else:
+            r = osc_model(f, a, b, omega, kind, rtol=rtol, atol=atol, panels=int(panels),
+                          max_depth=int(max_depth), max_intervals=int(max_intervals))
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in _OSC_FIELDS}
+    else:
+        raise ValueError("integrate_expr_oscillatory backend must be 'hip' or 'cpu'")
+    return OscillatoryResult(**fields, device_ms=ms, expr=expr, a=a, b=b, backend=backend)
+
+
+@dataclasses.dataclass
 class Adaptive2DResult:
     value: float
     err_est: float          # the sum of the accepted rectangles' |K15xK15 - G7xG7|

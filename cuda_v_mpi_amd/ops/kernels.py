@@ -518,6 +518,55 @@ def quad_expr(expr: str, a: float, b: float, rtol: float = 1e-10, atol: float = 
     return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
 
 
+_EXPR_OSC_CACHE: dict = {}
+
+
+def quad_expr_osc(expr: str, a: float, b: float, omega: float, kind: str = "cos",
+                  rtol: float = 1e-10, atol: float = 0.0, panels: int = 65536,
+                  max_depth: int = 60, max_intervals: int = 1 << 22,
+                  return_intervals: bool = False, tail_panels: int = 16, max_cycles: int = 50):
+    """The integral of f(x) cos(omega x) (``kind="sin"``: f(x) sin(omega x)) on [a, b] to the
+    tolerance max(atol, rtol * |value|), f one C++ expression over ``x`` and omega a number of
+    the call: adaptive Filon-Clenshaw-Curtis (13, 25), the weight integrated exactly and only f
+    interpolated, so the cost does not grow with omega. ``quad_expr``'s rounds and options around
+    two hipRTC-compiled evaluation kernels, cached with their module per (expression, device)
+    (csrc/runtime/expr_adaptive_osc.cpp). Both ends of every interval are evaluated: f must be
+    finite on the closed range. Returns the native OscResult: AdaptResult's fields (evals counts
+    25 per interval) and omega, kind, cycles, extrapolated, reason. With ``return_intervals``
+    also the final partition as two fp64 device tensors ``lo`` and ``hi``, running from a to b.
+    ``b = inf`` (a finite, omega != 0, atol > 0) is the Fourier tail: cycles of ``tail_panels``
+    panels, at most ``max_cycles`` of them, extrapolated by Wynn's epsilon algorithm; it returns
+    no partition."""
+    import math
+
+    m = native()
+    a, b, omega = float(a), float(b), float(omega)
+    tail = math.isinf(b) and b > 0 and math.isfinite(a)
+    opt = m.AdaptOptions(float(rtol), float(atol), int(panels), int(max_depth),
+                         int(max_intervals), False)
+    topt = m.OscTailOptions(int(tail_panels), int(max_cycles))
+    if kind not in ("cos", "sin"):
+        raise ValueError(f"oscillatory: kind '{kind}' must be cos or sin")
+    m.osc_check(a, b, omega, opt, tail, topt)  # before any device call
+    if tail and return_intervals:
+        raise ValueError("oscillatory: the Fourier tail returns no partition (return_intervals)")
+    m.expr_osc_source(expr)                    # a refused expression too
+    dev = _device()
+    key = (expr, dev.index)
+    eo = _EXPR_OSC_CACHE.get(key)
+    if eo is None:
+        eo = _EXPR_OSC_CACHE[key] = m.ExprAdaptiveOsc(expr, dev.index)
+    if tail:
+        return eo.integrate_tail(a, omega, kind, opt, topt)
+    if not return_intervals:
+        return eo.integrate(a, b, omega, kind, opt)
+    pairs = torch.empty((int(max_intervals), 2), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()  # the rounds run on their own stream
+    r = eo.integrate(a, b, omega, kind, opt, pairs.data_ptr(), int(max_intervals))
+    pairs = pairs[:r.intervals]
+    return r, pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+
+
 _EXPR_ADAPT2D_CACHE: dict = {}
 
 
