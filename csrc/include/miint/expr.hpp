@@ -368,7 +368,8 @@ class ExprIntegrator2D {
 //
 // Every family above sums n equally spaced samples and leaves n to the caller. Here the
 // Gauss-Kronrod (7, 15) pair is applied to a list of intervals, and the intervals whose
-// estimate misses their share of the tolerance are bisected, round by round (expr_adaptive.cpp).
+// estimate misses their share of the tolerance are bisected, round by round (expr_adaptive.cpp,
+// expr_adaptive_rounds.cpp).
 // On [lo, hi] with hw = 0.5 (hi - lo), c = lo + hw and nodes x_j = fma(hw, t_j, c):
 //   K = hw sum wk_j f(x_j) (15 nodes), G = hw sum wg_j f(x_j) (the 7 Gauss nodes among them),
 //   R = hw sum wk_j |f(x_j)|, err = |K - G|. Neither endpoint is evaluated.
@@ -395,6 +396,9 @@ class ExprIntegrator2D {
 //                        the other list (2 * exclusive prefix); the accepted intervals go to
 //                        the caller's buffer if one was given
 //
+// The host side of the rounds is detail::AdaptRounds (miint/expr_rtc.hpp), which ExprAdaptiveOsc,
+// ExprAdaptive2D and ExprAdaptiveRegion run around their own evaluation kernels too; the four
+// kernels behind the evaluation are one text for intervals and rectangles (adapt_round_source).
 // The host reads the record (the next count and the flags) after one sync per round and stops
 // when the next list is empty or the round was capped. No workgroup waits on another, the launch
 // shapes depend on the active count only and every sum has a fixed order: bitwise reproducible.
@@ -489,6 +493,11 @@ std::string expr_adapt_compile(const std::string& expr);
 // The eval kernels of the three infinite kinds (the rest of a round is expr_adapt_source's).
 std::string expr_adapt_unbounded_source(const std::string& expr);
 std::string expr_adapt_unbounded_compile(const std::string& expr);
+namespace detail {
+// The rounds' job (miint/expr_rtc.hpp) for one dimension: [lo, hi], lo < hi, under opt.
+AdaptJob adapt_job(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t capacity,
+                   bool descending = false);
+}  // namespace detail
 
 class ExprAdaptive {
  public:
@@ -507,36 +516,15 @@ class ExprAdaptive {
   const std::string& expression() const { return expr_; }
 
  private:
-  friend class ExprAdaptiveOsc;  // the same rounds and buffers around another evaluation kernel
-  // An evaluation kernel from another module in place of miint_adapt_eval: `launch` enqueues it
-  // on the rounds' stream for the n intervals of `list` and their depths, storing K, err, R and
-  // the workgroups' partials of K as miint_adapt_eval does; evals_per counts f per interval.
-  struct EvalTwin {
-    std::function<void(unsigned blocks, unsigned long long n, const double* list,
-                       const unsigned* depth)> launch;
-    uint64_t evals_per = 15;
-  };
-  void reserve(uint64_t max_intervals);
-  // kind kFinite: f on [lo, hi]; else g of that kind and `end` on [lo, hi] = [0, 1].
-  AdaptResult rounds(double lo, double hi, const AdaptOptions& opt, double* out, uint64_t cap,
-                     AdaptRange kind = AdaptRange::kFinite, double end = 0.0,
-                     const EvalTwin* twin = nullptr);
-  void load_unbounded();
+  // A call's range as the rounds take it: the job, and the evaluation launch of its kind.
+  detail::AdaptJob job(double a, double b, const AdaptOptions& opt, double* out,
+                       uint64_t capacity);
+  detail::AdaptRounds::Eval eval(double a, double b);
   std::string expr_;
-  int device_;
-  Stream stream_;
-  uint64_t reserved_ = 0;
-  DeviceBuffer<double> list_[2];        // (lo, hi) pairs: 2 x max_intervals doubles each
-  DeviceBuffer<unsigned> depth_[2];
-  DeviceBuffer<double> k_, err_, r_;    // per interval
-  DeviceBuffer<unsigned char> split_;   // per interval: 1 = bisect
-  DeviceBuffer<double> part_k_, blk_sums_;  // per workgroup: 1 and 5 doubles
-  DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 4 counters; the split prefix
-  DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive.cpp)
-  PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
-  Event e0_, e1_;
-  detail::RtcModule module_;  // the last members: destroyed first (miint/expr_rtc.hpp)
-  std::unique_ptr<detail::RtcModule> unbounded_;  // loaded at the first unbounded call
+  detail::AdaptRounds rounds_;  // with miint_adapt_eval
+  // the last member, destroyed before the rounds' stream (miint/expr_rtc.hpp): the twins of the
+  // infinite kinds, loaded at the first unbounded call
+  std::unique_ptr<detail::RtcModule> unbounded_;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -659,22 +647,23 @@ std::string osc_reason(const AdaptResult& r);
 class ExprAdaptiveOsc {
  public:
   ExprAdaptiveOsc(const std::string& expr, int device = 0);
-  // The integral of f(x) cos(omega x) (or sin) on [a, b] by ExprAdaptive's rounds around the
-  // rule above; intervals_out as ExprAdaptive::integrate. evals counts 25 per interval.
+  // The integral of f(x) cos(omega x) (or sin) on [a, b] by the rounds of intervals
+  // (detail::AdaptRounds, ExprAdaptive's) around the rule above; intervals_out as
+  // ExprAdaptive::integrate. evals counts 25 per interval.
   OscResult integrate(double a, double b, double omega, OscKind kind, const AdaptOptions& opt = {},
                       double* intervals_out = nullptr, uint64_t capacity = 0);
   // The same on (a, +inf) by the cycles above. opt.panels is not used (topt.panels is).
   OscResult integrate_tail(double a, double omega, OscKind kind, const AdaptOptions& opt,
                            const OscTailOptions& topt = {});
   double time(double a, double b, double omega, OscKind kind, const AdaptOptions& opt, int iters);
-  const std::string& expression() const { return rounds_.expression(); }
+  const std::string& expression() const { return expr_; }
   uint64_t table_uploads() const { return uploads_; }
 
  private:
   void upload(double par0, int rows, int upto);
-  AdaptResult run(double lo, double hi, double hw0, double omega, OscKind kind,
-                  const AdaptOptions& opt, double* out, uint64_t cap);
-  ExprAdaptive rounds_;  // its buffers and rounds around the twins
+  AdaptResult run(const detail::AdaptJob& job, double hw0, double omega, OscKind kind, bool timed);
+  std::string expr_;
+  detail::AdaptRounds rounds_;  // expr_adapt_source's module: its evaluation kernel is not used
   DeviceBuffer<double> table_;          // (max_depth + 1) x kOscRow
   std::vector<double> host_table_;
   double table_par0_ = 0.0;
@@ -717,7 +706,8 @@ class ExprAdaptiveOsc {
 // halves of one 32-bit word).
 //
 // The list starts as panels_x x panels_y equal rectangles, x fastest, each axis's edges formed
-// as miint_adapt_init forms them. A round is ExprAdaptive's: miint_adapt2d_eval (one rectangle
+// as miint_adapt_init forms them. A round is ExprAdaptive's, run by the same engine
+// (detail::AdaptRounds in two dimensions) on the same text: miint_adapt2d_eval (one rectangle
 // per lane; the loop over the 15 rows is rolled, a row's 15 evaluations unrolled in it),
 // _close (sum_K and tol = max(atol, rtol |S_acc + sum_K|) on the device), _decide, _prefix
 // (the cap: accepted + (n - splits) + 2 splits > max_intervals splits nothing and the pending
@@ -778,27 +768,17 @@ class ExprAdaptive2D {
   const std::string& expression() const { return expr_; }
 
  private:
-  friend class ExprAdaptiveRegion;  // the same rounds and buffers around another evaluation kernel
-  ExprAdaptive2D(const std::string& expr, const std::string& code, const char* eval, int device);
-  void reserve(uint64_t max_intervals);
-  Adapt2DResult rounds(double x0, double x1, double y0, double y1, const Adapt2DOptions& opt,
-                       double* out, uint64_t cap);
   std::string expr_;
-  int device_;
-  Stream stream_;
-  uint64_t reserved_ = 0;
-  DeviceBuffer<double> xs_[2], ys_[2];  // (x0, x1) and (y0, y1) pairs: 2 x max_intervals each
-  DeviceBuffer<unsigned> depth_[2];     // x depth | y depth << 16
-  DeviceBuffer<double> k_, err_, r_;    // per rectangle
-  DeviceBuffer<double> dir_;            // per rectangle: (ex, ey)
-  DeviceBuffer<unsigned char> split_;   // per rectangle: 0 accepted, 1 bisect x, 2 bisect y
-  DeviceBuffer<double> part_k_, blk_sums_;  // per workgroup: 1 and 5 doubles
-  DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 5 counters; the split prefix
-  DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive2d.cpp)
-  PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
-  Event e0_, e1_;
-  detail::RtcModule module_;  // the last member: destroyed first (miint/expr_rtc.hpp)
+  detail::AdaptRounds rounds_;  // with miint_adapt2d_eval
 };
+namespace detail {
+// ExprAdaptive2D::integrate and ::time on `rounds` (two dimensions), whose own evaluation kernel
+// takes miint_adapt2d_eval's arguments: the checks, the ends' order and sign, the rounds.
+Adapt2DResult adapt2d_integrate(AdaptRounds& rounds, double ax, double bx, double ay, double by,
+                                const Adapt2DOptions& opt, double* rects_out, uint64_t capacity);
+double adapt2d_time(AdaptRounds& rounds, double ax, double bx, double ay, double by,
+                    const Adapt2DOptions& opt, int iters);
+}  // namespace detail
 
 // ---------------------------------------------------------------------------------------
 // Adaptive double integrals between two curves: the integral of f(x, y) over the region
@@ -806,10 +786,11 @@ class ExprAdaptive2D {
 // run-time expressions over x alone.
 //
 // The region is mapped onto (x, v) in [ax, bx] x [0, 1] by y = g(x) + (h(x) - g(x)) v, and
-// ExprAdaptive2D's rounds run on the mapped integrand f(x, y(x, v)) (h(x) - g(x)) over that
-// rectangle. A rectangle of the list is [x0, x1] x [v0, v1]; the list starts as panels_x x
-// panels_y equal rectangles of [min(ax, bx), max(ax, bx)] x [0, 1], formed by
-// miint_adapt2d_init. Per rectangle (expr_adaptive_region.cpp, miint_region_gk15x15):
+// the rounds of rectangles (detail::AdaptRounds, ExprAdaptive2D's) run on the mapped integrand
+// f(x, y(x, v)) (h(x) - g(x)) over that rectangle. A rectangle of the list is [x0, x1] x
+// [v0, v1]; the list starts as panels_x x panels_y equal rectangles of [min(ax, bx), max(ax, bx)]
+// x [0, 1], formed by miint_adapt2d_init. Per rectangle (expr_adaptive_region.cpp,
+// miint_region_gk15x15):
 //   the x nodes x_i are ExprAdaptive2D's: cx and fma(hx, -+t_i, cx); the v nodes v_j are what it
 //   forms along y: cy and fma(hy, -+t_j, cy).
 //   Per x node, once per rectangle and in front of the loop over the rows:
@@ -819,7 +800,8 @@ class ExprAdaptive2D {
 // Everything after the 225 values is ExprAdaptive2D's with Wx = |bx - ax| and Wy = 1: the row
 // sums, the row combination, K, err, ex, ey, R, the split axis, the decision order, the depths,
 // the cap and the eighteen-word record. Of a round's six kernels only the evaluation kernel has
-// a twin (miint_region_eval); the other five are the text ExprAdaptive2D compiles.
+// a twin (miint_region_eval); the other five are the text ExprAdaptive2D compiles
+// (adapt_round_source), around an engine of its own.
 //
 // ax > bx negates; ax == bx gives 0 with no launch. Where h(x) < g(x), w_i is negative and that
 // strip counts negatively: the pointwise form of ay > by, neither refused nor clamped. A limit
@@ -849,13 +831,13 @@ class ExprAdaptiveRegion {
   Adapt2DResult integrate(double ax, double bx, const Adapt2DOptions& opt = {},
                           double* rects_out = nullptr, uint64_t capacity = 0);
   double time(double ax, double bx, const Adapt2DOptions& opt, int iters);
-  const std::string& expression() const { return rounds_.expression(); }
+  const std::string& expression() const { return expr_; }
   const std::string& y_lo() const { return ylo_; }
   const std::string& y_hi() const { return yhi_; }
 
  private:
-  std::string ylo_, yhi_;
-  ExprAdaptive2D rounds_;  // its buffers and rounds around miint_region_eval
+  std::string expr_, ylo_, yhi_;
+  detail::AdaptRounds rounds_;  // with miint_region_eval
 };
 
 // ---------------------------------------------------------------------------------------

@@ -1,6 +1,10 @@
 // What the run-time expression families (miint/expr.hpp: ExprIntegrator, ExprSweep, ExprScan,
 // ExprIntegrator2D) and their host counterparts share: the cached hipRTC compile, the owner
-// of a loaded module, the timing loop, the argument checks and the device prelude. Internal.
+// of a loaded module, the timing loop, the argument checks and the device prelude; and what the
+// adaptive families (ExprAdaptive, ExprAdaptiveSweep, ExprAdaptiveOsc, ExprAdaptive2D,
+// ExprAdaptiveRegion) share on top of that: the rules' text, the printer of an evaluation kernel,
+// the one source of a round's other kernels and the host engine of the rounds, AdaptRounds
+// (expr_adaptive_rounds.cpp). ExprAdaptiveSweep's rounds are its own. Internal.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,17 +39,38 @@ std::string adapt_rule_source(const std::string& expr, const std::string& sig,
 std::string adapt_unbounded_rule_source(const std::string& expr, const std::string& sig,
                                         const std::string& args);
 
-// The adaptive 2-D families' shared device text (expr_adaptive2d.cpp): ExprAdaptive2D's source is
-// the prelude, miint_f, the table, the row macros and miint_gk15x15 (its row loop printed by
-// adapt2d_row_source, closed by kAdapt2DCombine), kAdapt2DInit, the evaluation kernel and
-// kAdapt2DRound. ExprAdaptiveRegion replaces the function, the macros, the rule and the
-// evaluation kernel and carries the rest as it stands. adapt2d_row_source(true) also passes a
-// pair's two column numbers to its macro.
+// The adaptive 2-D families' rule (expr_adaptive2d.cpp): the table, a row's fifteen evaluations
+// (with `columns` a pair's macro also takes the numbers of its two columns, as ExprAdaptiveRegion's
+// macros want them) and the end of miint_gk15x15's row loop and of the rule. adapt2d_eval_source
+// is adapt_eval_source for a rectangle: `rule` is called on (xs[i], ys[i]).
 std::string adapt2d_table_source();
 std::string adapt2d_row_source(bool columns);
 extern const char* const kAdapt2DCombine;
-extern const char* const kAdapt2DInit;
-extern const char* const kAdapt2DRound;
+std::string adapt2d_eval_source(const std::string& comment, const std::string& name,
+                                const std::string& rule);
+
+// "%a" and "%.17g" of v, and the double whose bits are w.
+std::string hex(double v);
+std::string num(double v);
+double word_as_double(unsigned long long w);
+// The refusals every adaptive family words alike, `what` in front: rtol and atol, then
+// max_intervals; and max_depth, `per` behind it.
+void adapt_check_tolerances(const std::string& what, double rtol, double atol,
+                            uint64_t max_intervals);
+void adapt_check_depth(const std::string& what, int max_depth, const char* per = "");
+
+// An evaluation kernel of a round (expr_adaptive_rounds.cpp), printed: `comment`, then kernel
+// `name` over `params` (n first; k, err, r and part_k among them). Lane i < n runs `call`, whole
+// lines that load item i and leave K, err and R in v, e and a (declared by the call but for v),
+// and stores them, `stores` (whole lines, such as dir[i]) between err and r; the workgroup's
+// MIINT_BLOCK_SUM of v goes to part_k.
+std::string adapt_eval_source(const std::string& comment, const std::string& name,
+                              const std::string& params, const std::string& call,
+                              const std::string& stores = "");
+// A round's source behind the rule, for intervals (dims 1, miint_adapt_*) or rectangles (dims 2,
+// miint_adapt2d_*): MIINT_ST_D and _init, the family's evaluation kernel `eval`, then _close,
+// _decide, _prefix and _scatter, one text with the dimension's own parts passed into it.
+std::string adapt_round_source(int dims, const std::string& eval);
 
 // A loaded code object and its kernels. The destructor selects the device, drains the owning
 // object's stream and unloads: declare it as the owner's LAST member, after the Stream, the
@@ -91,6 +116,87 @@ double time_enqueues(const Stream& stream, Event& e0, Event& e1, int iters, Enqu
   stream.sync();
   return Event::elapsed_ms(e0, e1) / iters;
 }
+
+// One call of the adaptive rounds, checked by the caller. Per axis lo < hi; y0, y1 and py are
+// read in two dimensions only, `descending` in one.
+struct AdaptJob {
+  double x0, x1, y0, y1;
+  uint64_t px, py;         // the first list: px (x py) equal panels
+  double rtol, atol;
+  uint64_t max_intervals;
+  int max_depth;           // per axis
+  double* out;             // device memory for the partition (2 or 4 doubles an item), or null
+  uint64_t capacity;       // items `out` holds
+  bool descending;         // the partition from x1 down to x0, every pair swapped
+};
+
+// What an evaluation launch works on: n items in `blocks` workgroups of 256 on `stream`.
+struct AdaptItems {
+  hipStream_t stream;
+  unsigned blocks;
+  unsigned long long n;
+  const double2 *xs, *ys;  // the extents per axis (ys null in one dimension)
+  const unsigned* depth;
+  double *k, *err, *r;     // per item
+  double2* dir;            // per item, two dimensions only
+  double* part_k;          // per workgroup
+};
+
+// The rounds of ExprAdaptive, ExprAdaptiveOsc (dims 1), ExprAdaptive2D and ExprAdaptiveRegion
+// (dims 2): the stream, the lists and buffers, the state and its pinned record, the events and
+// the module of adapt_round_source's kernels. A round is the caller's evaluation launch, then
+// _close, _decide, _prefix and _scatter, one sync and a look at the record.
+// The contract of an evaluation launch: enqueued on AdaptItems::stream, it stores K, err and R
+// (and in two dimensions dir = (ex, ey)) of every item, and per workgroup of 256 items the sum
+// of its K in MIINT_BLOCK_SUM's order to part_k (adapt_eval_source prints such a kernel).
+// The helpers that need the option structs are declared beside them in miint/expr.hpp:
+// detail::adapt_job, detail::adapt2d_integrate and detail::adapt2d_time.
+class AdaptRounds {
+ public:
+  enum { kInit, kEval, kClose, kDecide, kPrefix, kScatter };  // module()'s kernels
+  using Eval = std::function<void(const AdaptItems&)>;
+  // `code` holds the five kernels of adapt_round_source(dims, ...) and the kernel `eval`.
+  AdaptRounds(int dims, const std::string& code, const char* eval, int device);
+  // Every buffer holds max_intervals items (or their workgroups): sized once for the largest
+  // max_intervals asked so far and kept across calls.
+  void reserve(uint64_t max_intervals);
+  // Throws unless `out` is null or holds max_intervals items. No device needed.
+  void check_capacity(const double* out, uint64_t capacity, uint64_t max_intervals) const;
+  // The rounds of one call; `evals_per` counts f per item. The partition goes to job.out in
+  // acceptance order. Result is AdaptResult or Adapt2DResult (miint/expr.hpp).
+  template <class Result>
+  Result run(const AdaptJob& job, uint64_t evals_per, const Eval& eval);
+  // run() between the two events (device_ms), then the partition ordered on the host: by lower
+  // end (or `descending`) in one dimension, by (y0, x0) in two.
+  template <class Result>
+  Result integrate(const AdaptJob& job, uint64_t evals_per, const Eval& eval);
+  // Device ms per `once()`, which enqueues on stream(): time_enqueues with the engine's events.
+  template <class Enqueue>
+  double time(int iters, Enqueue&& once) {
+    return time_enqueues(stream_, e0_, e1_, iters, once);
+  }
+  int device() const { return device_; }
+  const Stream& stream() const { return stream_; }
+  const RtcModule& module() const { return module_; }
+
+ private:
+  void order(const AdaptJob& job, uint64_t count);
+  int dims_, device_;
+  std::string what_;  // "adaptive" or "adaptive 2-D", in front of every message
+  Stream stream_;
+  uint64_t reserved_ = 0;
+  DeviceBuffer<double> xs_[2], ys_[2];  // (lo, hi) pairs per axis: 2 x max_intervals doubles each
+  DeviceBuffer<unsigned> depth_[2];     // two dimensions: x depth | y depth << 16
+  DeviceBuffer<double> k_, err_, r_;    // per item
+  DeviceBuffer<double> dir_;            // per rectangle: (ex, ey)
+  DeviceBuffer<unsigned char> split_;   // per item: 0 accepted, 1 bisect (x), 2 bisect y
+  DeviceBuffer<double> part_k_, blk_sums_;  // per workgroup: 1 and 5 doubles
+  DeviceBuffer<unsigned> blk_counts_, blk_off_;  // per workgroup: 4 or 5 counters; the split prefix
+  DeviceBuffer<unsigned long long> state_;   // the totals and counters (expr_adaptive_rounds.cpp)
+  PinnedBuffer<unsigned long long> record_;  // the same words, stored by the prefix kernel
+  Event e0_, e1_;
+  RtcModule module_;  // the last member: destroyed first (see RtcModule)
+};
 
 // n >= 1 and [begin, begin + count) lies in [0, n) without wrapping.
 inline bool slice_in_range(uint64_t n, uint64_t begin, uint64_t count) {

@@ -1,10 +1,10 @@
 // Adaptive Filon-Clenshaw-Curtis (13, 25) integration of a runtime f(x) against cos(omega x) or
-// sin(omega x) to a requested tolerance, and the Fourier tail on (a, +inf): ExprAdaptive's
-// rounds around another evaluation kernel (see miint/expr.hpp, ExprAdaptiveOsc).
+// sin(omega x) to a requested tolerance, and the Fourier tail on (a, +inf): the rounds of
+// intervals (detail::AdaptRounds) around another evaluation kernel (see miint/expr.hpp,
+// ExprAdaptiveOsc).
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <cstdio>
 #include <limits>
 
 #include "miint/expr.hpp"
@@ -49,17 +49,8 @@ using ld = long double;
 constexpr ld kPi = 3.14159265358979323846264338327950288L;
 constexpr ld kBesselBelow = 64.0L;  // |par| below this: the Bessel series; else forwards
 
-std::string hex(double v) {
-  char b[40];
-  std::snprintf(b, sizeof b, "%a", v);
-  return b;
-}
-
-std::string num(double v) {
-  char b[40];
-  std::snprintf(b, sizeof b, "%.17g", v);
-  return b;
-}
+using detail::hex;
+using detail::num;
 
 // int_{-1}^{1} T_k T_n dt
 ld cheb_pair(int k, int n) {
@@ -326,28 +317,15 @@ __device__ __forceinline__ void miint_osc_rule(double lo, double hi, const doubl
   // block sums and partials are the same.
   const char* names[2] = {"cos", "sin"};
   for (int kind = 0; kind < 2; ++kind)
-    src += std::string(R"(
-extern "C" __global__ __launch_bounds__(256) void miint_osc_eval_)") + names[kind] + R"((
-    unsigned long long n, const double2* __restrict__ list, const unsigned* __restrict__ depth,
+    src += "\n" + detail::adapt_eval_source(
+        "", std::string("miint_osc_eval_") + names[kind],
+        R"(unsigned long long n, const double2* __restrict__ list, const unsigned* __restrict__ depth,
     const double* __restrict__ table, unsigned rows, double omega, double* __restrict__ k,
-    double* __restrict__ err, double* __restrict__ r, double* __restrict__ part_k) {
-  __shared__ double red[4];
-  const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  double v = 0.0;
-  if (i < n) {
-    const double2 iv = list[i];
-    const unsigned d = depth[i] < rows ? depth[i] : rows - 1u;
-    double e, a;
-    miint_osc_rule(iv.x, iv.y, table + )" + std::to_string(kOscRow) + R"(ull * d, omega, )" +
-           std::to_string(kind) + R"(, &v, &e, &a);
-    k[i] = v;
-    err[i] = e;
-    r[i] = a;
-  }
-  MIINT_BLOCK_SUM(v, red);
-  if (threadIdx.x == 0) part_k[blockIdx.x] = MIINT_RED(red);
-}
-)";
+    double* __restrict__ err, double* __restrict__ r, double* __restrict__ part_k)",
+        "    const double2 iv = list[i];\n"
+        "    const unsigned d = depth[i] < rows ? depth[i] : rows - 1u;\n    double e, a;\n"
+        "    miint_osc_rule(iv.x, iv.y, table + " + std::to_string(kOscRow) + "ull * d, omega, " +
+            std::to_string(kind) + ", &v, &e, &a);\n");
   return src;
 }
 
@@ -392,15 +370,15 @@ std::string osc_reason(const AdaptResult& r) {
 }
 
 ExprAdaptiveOsc::ExprAdaptiveOsc(const std::string& expr, int device)
-    : rounds_(expr, device),
-      twins_(expr_osc_compile(expr), device, rounds_.stream_,
+    : expr_(expr), rounds_(1, expr_adapt_compile(expr), "miint_adapt_eval", device),
+      twins_(expr_osc_compile(expr), device, rounds_.stream(),
              {"miint_osc_eval_cos", "miint_osc_eval_sin"}) {}
 
 // Rows 0 .. upto of the table for par0 on the device: a row is computed and sent when the
 // first round that can hold its depth is about to be enqueued.
 void ExprAdaptiveOsc::upload(double par0, int rows, int upto) {
   if (static_cast<int>(host_table_.size()) < rows * kOscRow || table_rows_ < rows) {
-    rounds_.stream_.sync();
+    rounds_.stream().sync();
     host_table_.assign(static_cast<size_t>(rows) * kOscRow, 0.0);
     table_ = DeviceBuffer<double>(static_cast<size_t>(rows) * kOscRow);
     table_rows_ = rows;
@@ -417,28 +395,26 @@ void ExprAdaptiveOsc::upload(double par0, int rows, int upto) {
     osc_table_row(std::ldexp(par0, -d), row);
     MIINT_HIP(hipMemcpyAsync(table_.get() + static_cast<size_t>(d) * kOscRow, row,
                              kOscRow * sizeof(double), hipMemcpyHostToDevice,
-                             rounds_.stream_.get()));
+                             rounds_.stream().get()));
     table_depths_ = d + 1;
   }
 }
 
-// lo < hi. hw0 is the nominal half width of a first interval.
-AdaptResult ExprAdaptiveOsc::run(double lo, double hi, double hw0, double omega, OscKind kind,
-                                 const AdaptOptions& opt, double* out, uint64_t cap) {
+// The rounds of `job` around the twin of `kind`; hw0 is the nominal half width of a first
+// interval. `timed`: between the events, the partition ordered (AdaptRounds::integrate).
+AdaptResult ExprAdaptiveOsc::run(const detail::AdaptJob& job, double hw0, double omega,
+                                 OscKind kind, bool timed) {
   const double par0 = omega * hw0;
-  const int rows = opt.max_depth + 1;
+  const int rows = job.max_depth + 1;
   int round = 0;
-  ExprAdaptive::EvalTwin twin;
-  twin.evals_per = 25;
-  twin.launch = [&](unsigned blocks, unsigned long long n, const double* list,
-                    const unsigned* depth) {
+  const detail::AdaptRounds::Eval eval = [&](const detail::AdaptItems& it) {
     upload(par0, rows, round++);  // round t holds depths 0 .. t
-    twins_.launch(static_cast<size_t>(kind), blocks, 1, kOscBlock, rounds_.stream_.get(), n,
-                  reinterpret_cast<const double2*>(list), depth,
-                  static_cast<const double*>(table_.get()), static_cast<unsigned>(rows), omega,
-                  rounds_.k_.get(), rounds_.err_.get(), rounds_.r_.get(), rounds_.part_k_.get());
+    twins_.launch(static_cast<size_t>(kind), it.blocks, 1, kOscBlock, it.stream, it.n, it.xs,
+                  it.depth, static_cast<const double*>(table_.get()), static_cast<unsigned>(rows),
+                  omega, it.k, it.err, it.r, it.part_k);
   };
-  return rounds_.rounds(lo, hi, opt, out, cap, AdaptRange::kFinite, 0.0, &twin);
+  return timed ? rounds_.integrate<AdaptResult>(job, 25, eval)
+               : rounds_.run<AdaptResult>(job, 25, eval);
 }
 
 OscResult ExprAdaptiveOsc::integrate(double a, double b, double omega, OscKind kind,
@@ -450,9 +426,7 @@ OscResult ExprAdaptiveOsc::integrate(double a, double b, double omega, OscKind k
     return integrate_tail(a, omega, kind, opt);
   }
   osc_check(a, b, omega, opt);
-  MIINT_CHECK(intervals_out == nullptr || capacity >= opt.max_intervals,
-              "adaptive: intervals_out holds " + std::to_string(capacity) +
-                  " intervals, fewer than max_intervals = " + std::to_string(opt.max_intervals));
+  rounds_.check_capacity(intervals_out, capacity, opt.max_intervals);
   OscResult res;
   res.omega = omega;
   res.kind = osc_kind_name(kind);
@@ -461,32 +435,15 @@ OscResult ExprAdaptiveOsc::integrate(double a, double b, double omega, OscKind k
     res.converged = true;
     return res;
   }
-  DeviceGuard g(rounds_.device_);
+  DeviceGuard g(rounds_.device());
   rounds_.reserve(opt.max_intervals);
   const bool swapped = a > b;
   const double lo = swapped ? b : a, hi = swapped ? a : b;
   const double hw0 = 0.5 * ((hi - lo) / static_cast<double>(opt.panels));
-  rounds_.e0_.record(rounds_.stream_.get());
-  static_cast<AdaptResult&>(res) = run(lo, hi, hw0, omega, kind, opt, intervals_out, capacity);
-  rounds_.e1_.record(rounds_.stream_.get());
-  rounds_.stream_.sync();
-  res.device_ms = Event::elapsed_ms(rounds_.e0_, rounds_.e1_);
+  static_cast<AdaptResult&>(res) = run(
+      detail::adapt_job(lo, hi, opt, intervals_out, capacity, swapped), hw0, omega, kind, true);
   if (swapped) res.value = -res.value;
   res.reason = osc_reason(res);
-  if (intervals_out != nullptr) {
-    // as ExprAdaptive::integrate: acceptance order to x order, on the host
-    MIINT_CHECK(res.intervals <= capacity, "adaptive: the partition passed intervals_out");
-    std::vector<std::pair<double, double>> iv(res.intervals);
-    MIINT_HIP(hipMemcpy(iv.data(), intervals_out, iv.size() * 2 * sizeof(double),
-                        hipMemcpyDeviceToHost));
-    std::sort(iv.begin(), iv.end());
-    if (swapped) {
-      std::reverse(iv.begin(), iv.end());
-      for (auto& p : iv) std::swap(p.first, p.second);
-    }
-    MIINT_HIP(hipMemcpy(intervals_out, iv.data(), iv.size() * 2 * sizeof(double),
-                        hipMemcpyHostToDevice));
-  }
   return res;
 }
 
@@ -499,7 +456,7 @@ OscResult ExprAdaptiveOsc::integrate_tail(double a, double omega, OscKind kind,
   res.kind = osc_kind_name(kind);
   res.range = "upper";
   res.tol = opt.atol;
-  DeviceGuard g(rounds_.device_);
+  DeviceGuard g(rounds_.device());
   AdaptOptions o = opt;
   o.unbounded = false;
   o.rtol = 0.0;
@@ -517,11 +474,8 @@ OscResult ExprAdaptiveOsc::integrate_tail(double a, double omega, OscKind kind,
     const double hi = a + static_cast<double>(k) * cycle;
     o.atol = opt.atol * share;
     share = share * p;
-    rounds_.e0_.record(rounds_.stream_.get());
-    const AdaptResult r = run(lo, hi, hw0, omega, kind, o, nullptr, 0);
-    rounds_.e1_.record(rounds_.stream_.get());
-    rounds_.stream_.sync();
-    res.device_ms += Event::elapsed_ms(rounds_.e0_, rounds_.e1_);
+    const AdaptResult r = run(detail::adapt_job(lo, hi, o, nullptr, 0), hw0, omega, kind, true);
+    res.device_ms += r.device_ms;
     ++res.cycles;
     psum = psum + r.value;
     errsum = errsum + r.err_est;
@@ -580,12 +534,12 @@ double ExprAdaptiveOsc::time(double a, double b, double omega, OscKind kind,
   MIINT_CHECK(iters >= 1, "bad adaptive timing request");
   osc_check(a, b, omega, opt);
   if (a == b) return 0.0;
-  DeviceGuard g(rounds_.device_);
+  DeviceGuard g(rounds_.device());
   rounds_.reserve(opt.max_intervals);
   const double lo = std::min(a, b), hi = std::max(a, b);
   const double hw0 = 0.5 * ((hi - lo) / static_cast<double>(opt.panels));
-  return detail::time_enqueues(rounds_.stream_, rounds_.e0_, rounds_.e1_, iters,
-                               [&] { (void)run(lo, hi, hw0, omega, kind, opt, nullptr, 0); });
+  const detail::AdaptJob job = detail::adapt_job(lo, hi, opt, nullptr, 0);
+  return rounds_.time(iters, [&] { (void)run(job, hw0, omega, kind, false); });
 }
 
 }  // namespace miint

@@ -1,6 +1,6 @@
 // Adaptive double integrals of a runtime f(x, y) between two curves, y from ylo(x) to yhi(x):
-// the region mapped onto [ax, bx] x [0, 1] and ExprAdaptive2D's rounds on the mapped integrand,
-// the evaluation kernel replaced by its twin (see miint/expr.hpp, ExprAdaptiveRegion).
+// the region mapped onto [ax, bx] x [0, 1] and the rounds of rectangles (detail::AdaptRounds) on
+// the mapped integrand, around its own evaluation kernel (see miint/expr.hpp, ExprAdaptiveRegion).
 #include <cctype>
 #include <cstdio>
 #include <vector>
@@ -103,28 +103,12 @@ __device__ __forceinline__ void miint_region_gk15x15(double2 xr, double2 yr, dou
     const double t = miint_gk_t[j];
     const double v = row == 0 ? cy : fma(hy, (row & 1) ? -t : t, cy);
     double rk, rg, ra;
-)" + detail::adapt2d_row_source(true) + detail::kAdapt2DCombine + detail::kAdapt2DInit + R"(
-// One rectangle of (x, v) per lane: 30 limit evaluations, then the same 225 evaluations of the
-// mapped integrand in every lane. The arguments are miint_adapt2d_eval's.
-extern "C" __global__ __launch_bounds__(256) void miint_region_eval(
-    unsigned long long n, const double2* __restrict__ xs, const double2* __restrict__ ys,
-    double* __restrict__ k, double* __restrict__ err, double2* __restrict__ dir,
-    double* __restrict__ r, double* __restrict__ part_k) {
-  __shared__ double red[4];
-  const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  double v = 0.0;
-  if (i < n) {
-    double e, ex, ey, a;
-    miint_region_gk15x15(xs[i], ys[i], &v, &e, &ex, &ey, &a);
-    k[i] = v;
-    err[i] = e;
-    dir[i] = make_double2(ex, ey);
-    r[i] = a;
-  }
-  MIINT_BLOCK_SUM(v, red);
-  if (threadIdx.x == 0) part_k[blockIdx.x] = MIINT_RED(red);
-}
-)" + detail::kAdapt2DRound;
+)" + detail::adapt2d_row_source(true) + detail::kAdapt2DCombine +
+         detail::adapt_round_source(2, detail::adapt2d_eval_source(
+             "// One rectangle of (x, v) per lane: 30 limit evaluations, then the same 225 "
+             "evaluations of the\n// mapped integrand in every lane. The arguments are "
+             "miint_adapt2d_eval's.\n",
+             "miint_region_eval", "miint_region_gk15x15"));
 }
 
 std::string expr_region_compile(const std::string& expr, const std::string& ylo,
@@ -135,16 +119,16 @@ std::string expr_region_compile(const std::string& expr, const std::string& ylo,
 
 ExprAdaptiveRegion::ExprAdaptiveRegion(const std::string& expr, const std::string& ylo,
                                        const std::string& yhi, int device)
-    : ylo_(ylo), yhi_(yhi),
-      rounds_(expr, expr_region_compile(expr, ylo, yhi), "miint_region_eval", device) {}
+    : expr_(expr), ylo_(ylo), yhi_(yhi),
+      rounds_(2, expr_region_compile(expr, ylo, yhi), "miint_region_eval", device) {}
 
 Adapt2DResult ExprAdaptiveRegion::integrate(double ax, double bx, const Adapt2DOptions& opt,
                                             double* rects_out, uint64_t capacity) {
-  return rounds_.integrate(ax, bx, 0.0, 1.0, opt, rects_out, capacity);
+  return detail::adapt2d_integrate(rounds_, ax, bx, 0.0, 1.0, opt, rects_out, capacity);
 }
 
 double ExprAdaptiveRegion::time(double ax, double bx, const Adapt2DOptions& opt, int iters) {
-  return rounds_.time(ax, bx, 0.0, 1.0, opt, iters);
+  return detail::adapt2d_time(rounds_, ax, bx, 0.0, 1.0, opt, iters);
 }
 
 }  // namespace miint

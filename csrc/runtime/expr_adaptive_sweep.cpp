@@ -2,8 +2,6 @@
 // own tolerance, in shared rounds (see miint/expr.hpp, ExprAdaptiveSweep).
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 
 #include "miint/expr.hpp"
 
@@ -20,17 +18,8 @@ enum { kAccepted = 8, kSplits, kFloor, kForced, kNonfinite, kNext, kCapped };
 constexpr size_t kRowWords = 16;
 enum { kRecTotal, kRecActive, kRecordWords };
 
-double word_as_double(unsigned long long w) {
-  double d;
-  std::memcpy(&d, &w, sizeof d);
-  return d;
-}
-
-std::string num(double v) {
-  char b[40];
-  std::snprintf(b, sizeof b, "%.17g", v);
-  return b;
-}
+using detail::num;
+using detail::word_as_double;
 
 int checked_nparams(int nparams) {
   MIINT_CHECK(nparams >= 0 && nparams <= kSweepMaxParams,
@@ -38,6 +27,20 @@ int checked_nparams(int nparams) {
                   std::to_string(kSweepMaxParams));
   return nparams;
 }
+
+// The parameters' three spellings: ", double p0, ..." in a signature, "const double p0 = pr[0];
+// ..." as a kernel's loads of its row, ", p0, ..." at a call.
+struct ParamText {
+  std::string sig, load, args;
+  explicit ParamText(int nparams) {
+    for (int j = 0; j < checked_nparams(nparams); ++j) {
+      const std::string p = "p" + std::to_string(j);
+      sig += ", double " + p;
+      load += "  const double " + p + " = pr[" + std::to_string(j) + "];\n";
+      args += ", " + p;
+    }
+  }
+};
 }  // namespace
 
 uint64_t adapt_sweep_default_panels(uint64_t rows) {
@@ -80,15 +83,9 @@ AdaptSweepOptions adapt_sweep_check(uint64_t rows, int nparams, uint64_t param_c
 
 std::string expr_adapt_sweep_source(const std::string& expr, int nparams) {
   detail::expr_check_named(expr);
-  checked_nparams(nparams);
-  std::string sig, load, args;  // ", double p0, ..." / "const double p0 = pr[0]; ..." / ", p0, ..."
-  for (int j = 0; j < nparams; ++j) {
-    const std::string p = "p" + std::to_string(j);
-    sig += ", double " + p;
-    load += "  const double " + p + " = pr[" + std::to_string(j) + "];\n";
-    args += ", " + p;
-  }
-  return std::string(detail::kRtcPrelude) + detail::adapt_rule_source(expr, sig, args) +
+  const ParamText params(nparams);
+  return std::string(detail::kRtcPrelude) +
+         detail::adapt_rule_source(expr, params.sig, params.args) +
          "\n#define MIINT_NPARAMS " + std::to_string(nparams) + "u\n" + R"(
 // A row's words: 0..4 as doubles S_acc, E_acc, R_acc, tol, sum_K; 5 evals, 6 the last round the
 // row was active in; 8..14: accepted, splits, floor, forced, nonfinite, next, capped.
@@ -131,8 +128,8 @@ extern "C" __global__ __launch_bounds__(256) void miint_asweep_eval(
   const double2 iv = list[i];
   const double* __restrict__ pr = params + (unsigned long long)row[i] * MIINT_NPARAMS;
   (void)pr;
-)" + load + R"(  double v, e, s;
-  miint_gk15(iv.x, iv.y)" + args + R"(, &v, &e, &s);
+)" + params.load + R"(  double v, e, s;
+  miint_gk15(iv.x, iv.y)" + params.args + R"(, &v, &e, &s);
   k[i] = v;
   err[i] = e;
   r[i] = s;
@@ -302,16 +299,9 @@ extern "C" __global__ __launch_bounds__(256) void miint_asweep_scatter(
 
 std::string expr_adapt_sweep_unbounded_source(const std::string& expr, int nparams) {
   detail::expr_check_named(expr);
-  checked_nparams(nparams);
-  std::string sig, load, args;  // as in expr_adapt_sweep_source
-  for (int j = 0; j < nparams; ++j) {
-    const std::string p = "p" + std::to_string(j);
-    sig += ", double " + p;
-    load += "  const double " + p + " = pr[" + std::to_string(j) + "];\n";
-    args += ", " + p;
-  }
+  const ParamText params(nparams);
   std::string src = std::string(detail::kRtcPrelude) +
-                    detail::adapt_unbounded_rule_source(expr, sig, args) +
+                    detail::adapt_unbounded_rule_source(expr, params.sig, params.args) +
                     "\n#define MIINT_NPARAMS " + std::to_string(nparams) + "u\n";
   // miint_asweep_eval's twins: the interval is one of t in [0, 1] (miint/expr.hpp has the map).
   const char* names[3] = {"upper", "lower", "both"};
@@ -326,8 +316,8 @@ extern "C" __global__ __launch_bounds__(256) void miint_asweep_eval_)") + names[
   const double2 iv = list[i];
   const double* __restrict__ pr = params + (unsigned long long)row[i] * MIINT_NPARAMS;
   (void)pr;
-)" + load + R"(  double v, e, s;
-  miint_gk15(iv.x, iv.y, )" + std::to_string(kind) + ", end" + args + R"(, &v, &e, &s);
+)" + params.load + R"(  double v, e, s;
+  miint_gk15(iv.x, iv.y, )" + std::to_string(kind) + ", end" + params.args + R"(, &v, &e, &s);
   k[i] = v;
   err[i] = e;
   r[i] = s;
