@@ -757,8 +757,79 @@ int run_expr_adaptive2d(const cli::Args& a, const RiemannConfig& cfg) {
   return 0;
 }
 
+// Arrays of a --json record. %.17g round-trips a finite value; a non-finite one prints as null,
+// its bits are in the record's value_bits.
+std::string json_doubles(const std::vector<double>& v) {
+  std::string s = "[";
+  for (size_t k = 0; k < v.size(); ++k) {
+    char b[40];
+    if (std::isfinite(v[k])) std::snprintf(b, sizeof b, "%s%.17g", k ? "," : "", v[k]);
+    else std::snprintf(b, sizeof b, "%snull", k ? "," : "");
+    s += b;
+  }
+  return s + "]";
+}
+std::string json_counts(const std::vector<uint64_t>& v) {
+  std::string s = "[";
+  for (size_t k = 0; k < v.size(); ++k)
+    s += (k ? "," : "") + std::to_string(static_cast<unsigned long long>(v[k]));
+  return s + "]";
+}
+std::string json_flags(const std::vector<uint8_t>& v) {
+  std::string s = "[";
+  for (size_t k = 0; k < v.size(); ++k) s += std::string(k ? "," : "") + (v[k] ? "true" : "false");
+  return s + "]";
+}
+std::string json_bits(const std::vector<double>& v) {
+  std::string bits = "[";
+  for (size_t k = 0; k < v.size(); ++k) {
+    char b[24];
+    uint64_t w = 0;
+    std::memcpy(&w, &v[k], sizeof w);
+    std::snprintf(b, sizeof b, "%s\"%016llx\"", k ? "," : "", static_cast<unsigned long long>(w));
+    bits += b;
+  }
+  return bits + "]";
+}
+
+// The lines of a text file, `columns` numbers each, row-major (blank lines and lines that begin
+// with # are skipped); anything else is refused, naming the line.
+std::vector<double> load_columns(const std::string& path, int columns, const std::string& flag,
+                                 const std::string& what) {
+  std::FILE* f = std::fopen(path.c_str(), "r");
+  MIINT_CHECK(f != nullptr, flag + " " + path + ": cannot open the file");
+  std::vector<double> out;
+  char line[512];
+  for (int n = 1; std::fgets(line, sizeof line, f); ++n) {
+    const char* s = line;
+    while (*s == ' ' || *s == '\t') ++s;
+    if (*s == '\0' || *s == '\n' || *s == '\r' || *s == '#') continue;
+    int got = 0;
+    bool ok = true;
+    for (;;) {
+      char* end = nullptr;
+      const double v = std::strtod(s, &end);
+      if (end == s) break;
+      if (++got <= columns) out.push_back(v);
+      s = end;
+    }
+    while (*s == ' ' || *s == '\t' || *s == '\n' || *s == '\r') ++s;
+    ok = got == columns && *s == '\0';
+    if (!ok) {
+      std::fclose(f);
+      std::string text(line);
+      while (!text.empty() && (text.back() == '\n' || text.back() == '\r')) text.pop_back();
+      fail(flag + " " + path + ": line " + std::to_string(n) + ": expected `" + what +
+               "`, got '" + text + "'", __FILE__, __LINE__);
+    }
+  }
+  std::fclose(f);
+  return out;
+}
+
 // --expr with --params / --linspace and --row-rtol / --row-atol: every row to its own tolerance
-// in shared rounds (ExprAdaptiveSweep). One GPU, one rank. Refusals come before any device call.
+// in shared rounds (ExprAdaptiveSweep), on the shared [--a, --b] or, with --ranges FILE, on a
+// range per row. One GPU, one rank. Refusals come before any device call.
 bool row_adaptive_requested(const cli::Args& a) { return a.has("row-rtol") || a.has("row-atol"); }
 
 int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
@@ -792,16 +863,33 @@ int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
   o.max_depth = static_cast<int>(depth);
   o.max_intervals = static_cast<uint64_t>(max_iv);
   o.max_total = static_cast<uint64_t>(max_total);
-  o.unbounded = true;  // an infinity here was typed: --a -inf, --b inf
+  const bool ranged = a.has("ranges");
+  MIINT_CHECK(!ranged || !(a.has("a") || a.has("b")),
+              "--ranges gives every row its own a and b: --a / --b do not go with it");
+  o.unbounded = !ranged;  // an infinity here was typed: --a -inf, --b inf
   const SweepRows sw = sweep_rows(a);
+  std::vector<double> lo, hi;  // --ranges FILE: K lines `a b`
+  if (ranged) {
+    const std::string path = a.str("ranges", "");
+    const std::vector<double> ends = load_columns(path, 2, "--ranges", "a b");
+    MIINT_CHECK(ends.size() == 2 * sw.rows,
+                "--ranges " + path + ": " + std::to_string(ends.size() / 2) + " ranges for " +
+                    std::to_string(sw.rows) + " rows");
+    for (uint64_t k = 0; k < sw.rows; ++k) {
+      lo.push_back(ends[2 * k]);
+      hi.push_back(ends[2 * k + 1]);
+    }
+  }
   const AdaptSweepOptions used =
-      adapt_sweep_check(sw.rows, sw.nparams, sw.params.size(), cfg.a, cfg.b, o);
+      ranged ? adapt_sweep_ranges_check(sw.rows, sw.nparams, sw.params.size(), lo, hi, o)
+             : adapt_sweep_check(sw.rows, sw.nparams, sw.params.size(), cfg.a, cfg.b, o);
   const std::string expr = a.str("expr", "");
   (void)expr_adapt_sweep_source(expr, sw.nparams);  // a rejected expression: before any device call
   MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
   set_device(0);
   ExprAdaptiveSweep es(expr, sw.nparams, 0);
-  const AdaptSweepResult r = es.integrate(sw.params, sw.rows, cfg.a, cfg.b, o);
+  const AdaptSweepResult r = ranged ? es.integrate_ranges(sw.params, sw.rows, lo, hi, o)
+                                    : es.integrate(sw.params, sw.rows, cfg.a, cfg.b, o);
   const double secs = wall_seconds() - process_start_seconds();
   uint64_t missed = 0;
   for (uint8_t c : r.converged) missed += c ? 0 : 1;
@@ -816,51 +904,23 @@ int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
       for (int j = 0; j < sw.nparams; ++j) std::printf(" %.17g", sw.params[k * sw.nparams + j]);
       std::printf(" %.17g\n", r.value[k]);
     }
-  // %.17g round-trips a finite value; a non-finite one prints as null, its bits are in value_bits
-  auto doubles = [](const std::vector<double>& v) {
-    std::string s = "[";
-    for (size_t k = 0; k < v.size(); ++k) {
-      char b[40];
-      if (std::isfinite(v[k])) std::snprintf(b, sizeof b, "%s%.17g", k ? "," : "", v[k]);
-      else std::snprintf(b, sizeof b, "%snull", k ? "," : "");
-      s += b;
-    }
-    return s + "]";
-  };
-  auto counts = [](const std::vector<uint64_t>& v) {
-    std::string s = "[";
-    for (size_t k = 0; k < v.size(); ++k)
-      s += (k ? "," : "") + std::to_string(static_cast<unsigned long long>(v[k]));
-    return s + "]";
-  };
-  auto flags = [](const std::vector<uint8_t>& v) {
-    std::string s = "[";
-    for (size_t k = 0; k < v.size(); ++k) s += std::string(k ? "," : "") + (v[k] ? "true" : "false");
-    return s + "]";
-  };
-  std::string bits = "[";
-  for (size_t k = 0; k < r.value.size(); ++k) {
-    char b[24];
-    uint64_t w = 0;
-    std::memcpy(&w, &r.value[k], sizeof w);
-    std::snprintf(b, sizeof b, "%s\"%016llx\"", k ? "," : "", static_cast<unsigned long long>(w));
-    bits += b;
-  }
-  bits += "]";
+  const std::string bits = json_bits(r.value);
   cli::JsonRecord rec;
-  rec.add("program", "riemann").add("expr", expr).add("a", cfg.a).add("b", cfg.b)
-      .add("rows", static_cast<double>(sw.rows)).add("nparams", sw.nparams)
+  rec.add("program", "riemann").add("expr", expr);
+  if (ranged) rec.add_raw("a", json_doubles(lo)).add_raw("b", json_doubles(hi));
+  else rec.add("a", cfg.a).add("b", cfg.b);
+  rec.add("rows", static_cast<double>(sw.rows)).add("nparams", sw.nparams)
       .add("rtol", used.rtol).add("atol", used.atol)
       .add("panels", static_cast<double>(used.panels)).add("max_depth", used.max_depth)
       .add("max_intervals", static_cast<double>(used.max_intervals))
       .add("max_total", static_cast<double>(used.max_total))
-      .add_raw("value", doubles(r.value)).add_raw("value_bits", bits)
-      .add_raw("err_est", doubles(r.err_est)).add_raw("resabs", doubles(r.resabs))
-      .add_raw("tol", doubles(r.tol)).add_raw("converged", flags(r.converged))
-      .add_raw("evals", counts(r.evals)).add_raw("rounds", counts(r.rounds))
-      .add_raw("intervals", counts(r.intervals)).add_raw("splits", counts(r.splits))
-      .add_raw("floor", counts(r.floor)).add_raw("forced", counts(r.forced))
-      .add_raw("nonfinite", counts(r.nonfinite)).add_raw("capped", flags(r.capped))
+      .add_raw("value", json_doubles(r.value)).add_raw("value_bits", bits)
+      .add_raw("err_est", json_doubles(r.err_est)).add_raw("resabs", json_doubles(r.resabs))
+      .add_raw("tol", json_doubles(r.tol)).add_raw("converged", json_flags(r.converged))
+      .add_raw("evals", json_counts(r.evals)).add_raw("rounds", json_counts(r.rounds))
+      .add_raw("intervals", json_counts(r.intervals)).add_raw("splits", json_counts(r.splits))
+      .add_raw("floor", json_counts(r.floor)).add_raw("forced", json_counts(r.forced))
+      .add_raw("nonfinite", json_counts(r.nonfinite)).add_raw("capped", json_flags(r.capped))
       .add("not_converged", static_cast<double>(missed))
       .add("call_rounds", static_cast<double>(r.call_rounds))
       .add("call_evals", static_cast<double>(r.call_evals))
@@ -869,6 +929,115 @@ int run_expr_adaptive_sweep(const cli::Args& a, const RiemannConfig& cfg) {
   return 0;
 }
 
+
+// --expr with --curve-rtol / --curve-atol: the running integral F(x_j) from x_0 on a grid, every
+// cell to a tolerance (ExprAdaptiveCurve). The grid is --a A --b B --points M (M equal cells) or
+// --at FILE (one point per line). One GPU, one rank. Refusals come before any device call.
+bool curve_requested(const cli::Args& a) {
+  return a.has("curve-rtol") || a.has("curve-atol") || a.has("points") || a.has("at");
+}
+
+int run_expr_curve(const cli::Args& a) {
+  const std::string who = "--curve-rtol / --curve-atol";
+  MIINT_CHECK(a.has("curve-rtol") || a.has("curve-atol"),
+              "--points / --at are the grid of a running integral to a tolerance: they need " +
+                  who);
+  MIINT_CHECK(a.has("expr"), who + " are the tolerance of an --expr running integral");
+  for (const char* k : {"n", "rule", "running", "every", "running-out", "rtol", "atol",
+                        "row-rtol", "row-atol", "ranges", "area-rtol", "area-atol", "panels-y",
+                        "y-lo", "y-hi", "ya", "yb", "ny", "box", "osc", "omega", "max-cycles",
+                        "params", "linspace", "loopback", "m", "shifts", "seed", "z", "periodic",
+                        "m-max"})
+    MIINT_CHECK(!a.has(k), who + " are the tolerance of a running integral on a grid: --" + k +
+                               " does not go with them");
+  MIINT_CHECK(a.integer("gpus", 1) <= 1, who + " run on one GPU: --gpus " + a.str("gpus", "") +
+                                             " does not go with them");
+  MIINT_CHECK(cli::env_int("WORLD_SIZE", 1) <= 1,
+              who + " run as one rank: a rank environment (WORLD_SIZE = " +
+                  std::to_string(cli::env_int("WORLD_SIZE", 1)) + ") does not go with them");
+  MIINT_CHECK(!cli::on_cpu(a), who + " have no host engine: --device cpu does not go with them");
+  std::vector<double> x;
+  if (a.has("at")) {
+    MIINT_CHECK(!(a.has("a") || a.has("b") || a.has("points")),
+                "--at FILE is the whole grid: --a / --b / --points do not go with it");
+    x = load_columns(a.str("at", ""), 1, "--at", "x");
+  } else {
+    MIINT_CHECK(a.has("a") && a.has("b") && a.has("points"),
+                who + " need a grid: --a A --b B --points M, or --at FILE");
+    const double lo = a.num("a", 0.0), hi = a.num("b", 0.0);
+    MIINT_CHECK(!std::isinf(lo) && !std::isinf(hi),
+                who + " take a finite grid: --a " + a.str("a", "") + " --b " + a.str("b", "") +
+                    " has an infinite end");
+    const double cells = adaptive_number(a, "points", 0.0, true);
+    MIINT_CHECK(cells >= 1 && cells <= static_cast<double>(kAdaptCurveMaxCells),
+                "--points " + a.str("points", "") + " must be 1..2^20");
+    const uint64_t m = static_cast<uint64_t>(cells);
+    // x_j = a + ((b - a) j) / M, the last one b: the adaptive rules' edges
+    for (uint64_t j = 0; j <= m; ++j)
+      x.push_back(j == m ? hi : lo + ((hi - lo) * static_cast<double>(j)) / cells);
+  }
+  AdaptSweepOptions o;
+  o.rtol = adaptive_number(a, "curve-rtol", o.rtol, false);
+  o.atol = adaptive_number(a, "curve-atol", 0.0, false);
+  const double panels = adaptive_number(a, "panels", 0.0, true);
+  const double depth = adaptive_number(a, "max-depth", o.max_depth, true);
+  const double max_iv = adaptive_number(a, "max-intervals", 0.0, true);
+  const double max_total = adaptive_number(a, "max-total", static_cast<double>(o.max_total), true);
+  MIINT_CHECK(panels >= 0 && max_iv >= 0 && max_total >= 0 && std::fabs(depth) < 1e9,
+              "--panels, --max-intervals, --max-total and --max-depth must not be negative or "
+              "huge");
+  o.panels = static_cast<uint64_t>(panels);
+  o.max_depth = static_cast<int>(depth);
+  o.max_intervals = static_cast<uint64_t>(max_iv);
+  o.max_total = static_cast<uint64_t>(max_total);
+  const AdaptSweepOptions used = adapt_curve_check(x, o);
+  const std::string expr = a.str("expr", "");
+  (void)expr_adapt_sweep_source(expr, 0);  // a rejected expression: before any device call
+  MIINT_CHECK(device_count() >= 1, who + " need a HIP device (no HIP devices visible)");
+  set_device(0);
+  ExprAdaptiveCurve ec(expr, 0);
+  const AdaptCurveResult r = ec.integrate(x, o);
+  const double secs = wall_seconds() - process_start_seconds();
+  if (r.unconverged) {
+    uint64_t first = 0;
+    while (first < r.cells.rows() && r.cells.converged[first]) ++first;
+    std::fprintf(stderr, "riemann: not converged: %llu of %llu cells, the first one cell %llu "
+                 "(see converged per point and capped, nonfinite and forced per cell with "
+                 "--json)\n", static_cast<unsigned long long>(r.unconverged),
+                 static_cast<unsigned long long>(r.cells.rows()),
+                 static_cast<unsigned long long>(first));
+  }
+  if (!a.flag("json"))
+    for (uint64_t j = 0; j < r.points(); ++j)
+      std::printf("%.17g %.17g %.3g\n", r.x[j], r.value[j], r.err_est[j]);
+  const AdaptSweepResult& c = r.cells;
+  cli::JsonRecord cells;
+  cells.add_raw("value", json_doubles(c.value)).add_raw("err_est", json_doubles(c.err_est))
+      .add_raw("resabs", json_doubles(c.resabs)).add_raw("tol", json_doubles(c.tol))
+      .add_raw("converged", json_flags(c.converged)).add_raw("evals", json_counts(c.evals))
+      .add_raw("rounds", json_counts(c.rounds)).add_raw("intervals", json_counts(c.intervals))
+      .add_raw("splits", json_counts(c.splits)).add_raw("floor", json_counts(c.floor))
+      .add_raw("forced", json_counts(c.forced)).add_raw("nonfinite", json_counts(c.nonfinite))
+      .add_raw("capped", json_flags(c.capped));
+  cli::JsonRecord rec;
+  rec.add("program", "riemann").add("expr", expr)
+      .add("points", static_cast<double>(r.points())).add("rtol", used.rtol)
+      .add("atol", used.atol).add("panels", static_cast<double>(used.panels))
+      .add("max_depth", used.max_depth)
+      .add("max_intervals", static_cast<double>(used.max_intervals))
+      .add("max_total", static_cast<double>(used.max_total))
+      .add_raw("x", json_doubles(r.x)).add_raw("value", json_doubles(r.value))
+      .add_raw("value_bits", json_bits(r.value)).add_raw("err_est", json_doubles(r.err_est))
+      .add_raw("tol", json_doubles(r.tol)).add_raw("resabs", json_doubles(r.resabs))
+      .add_raw("converged", json_flags(r.converged))
+      .add_raw("atol_cell", json_doubles(r.atol_cell)).add_raw("cells", cells.str())
+      .add("total", r.total).add("not_converged", static_cast<double>(r.unconverged))
+      .add("call_rounds", static_cast<double>(r.call_rounds))
+      .add("call_evals", static_cast<double>(r.call_evals))
+      .add("peak", static_cast<double>(r.peak));
+  cli::emit(a, rec.add("device_ms", r.device_ms).add("seconds_wall", secs));
+  return 0;
+}
 
 // --expr with --box A0:B0,A1:B1,...: the integral of f(x0, ..., x{d-1}) over the box by a
 // randomly shifted rank-1 lattice rule (ExprLattice). --m M: the rule of n = 2^M points; --rtol R
@@ -1093,6 +1262,10 @@ constexpr const char* kUsage =
     "                [--panels P] [--max-depth D] [--max-intervals M] [--max-cycles C]]\n"
     "               [--expr EXPR --a A --b B --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
     "                [--row-atol T] [--panels P] [--max-depth D] [--max-intervals M] [--max-total N]]\n"
+    "               [--expr EXPR --ranges FILE --params FILE | --linspace p0=LO:HI:COUNT --row-rtol R\n"
+    "                [--row-atol T] [--panels P] [--max-depth D] [--max-intervals M] [--max-total N]]\n"
+    "               [--expr EXPR --a A --b B --points M | --at FILE --curve-rtol R [--curve-atol T]\n"
+    "                [--panels P] [--max-depth D] [--max-intervals M] [--max-total N]]\n"
     "               [--expr EXPR --box A0:B0,A1:B1,... --m M | --rtol R [--atol T] [--m-max M]\n"
     "                [--shifts R] [--seed S] [--periodic] [--z Z0,Z1,...] [--analytic V]]\n"
     "Riemann sum of f on [a, b] (default sin on [0, pi], N = 1e9); prints the reference's\n"
@@ -1159,6 +1332,20 @@ constexpr const char* kUsage =
     "  resabs, tol, converged, evals, rounds, intervals, splits, floor, forced, nonfinite, capped,\n"
     "  and rows, call_rounds, call_evals, peak, device_ms. Refused with --rtol, --atol, --n, --rule,\n"
     "  --running, --ya, --box, --gpus above 1, --loopback, WORLD_SIZE above 1 or --device cpu.\n"
+    "  --ranges FILE (K lines 'a b') in place of --a / --b: row r on its own finite [a_r, b_r],\n"
+    "  bitwise what the one-row call on that range gives; a_r > b_r negates the row, a_r == b_r\n"
+    "  gives 0. Refused with --a / --b, without a row tolerance, and with an infinite end.\n"
+    "--curve-rtol R / --curve-atol T: the running integral F(x_j) of --expr from x_0 at the points\n"
+    "  of a grid, --a A --b B --points M (M equal cells) or --at FILE (one point per line, strictly\n"
+    "  increasing or strictly decreasing): every cell to max(T |cell| / |grid|, R |its integral|),\n"
+    "  so err_est at a point is held to at most T + R * (the integral of |f| up to it). --panels P\n"
+    "  and --max-intervals M are per cell (default: 65536 / cells as a power of two, at least 1;\n"
+    "  --max-total / cells); --max-total N, --max-depth D. Prints 'x F err_est' lines and one\n"
+    "  warning on stderr if a cell did not converge; --json: the per-point arrays x, value,\n"
+    "  value_bits, err_est, tol, resabs, converged, the per-cell arrays in cells, atol_cell, total,\n"
+    "  call_rounds, call_evals, peak, device_ms. Refused with --n, --rule, --running, --rtol,\n"
+    "  --row-rtol, --area-rtol, --ya, --box, --osc, --params, --gpus above 1, --loopback,\n"
+    "  WORLD_SIZE above 1, --device cpu, an infinite end, --at with --a / --b / --points.\n"
     "--box A0:B0,A1:B1,...: the integral of --expr over x0, x1, ... (at most 16 sides) by a randomly\n"
     "  shifted rank-1 lattice rule: --m M for n = 2^M points (built-in generating vectors for M =\n"
     "  10..26, else --z Z0,Z1,... odd and below n), --shifts R random shifts (default 16) from\n"
@@ -1174,6 +1361,10 @@ int main(int argc, char** argv) {
     install_crash_handler_from_env();
     cli::Args a(argc, argv);
     if (cli::usage_requested(a, kUsage)) return 0;
+    if (curve_requested(a)) return run_expr_curve(a);  // it names its own conflicts
+    MIINT_CHECK(row_adaptive_requested(a) || !a.has("ranges"),
+                "--ranges gives the rows of a sweep to a tolerance their own ranges: it needs "
+                "--row-rtol R / --row-atol T");
     const Integrand f = cli::parse_integrand(a.str("integrand", "sin"));
     const double pi = 3.14159265358979323846;
     double lo = 0.0, hi = pi;  // riemann.cpp:6 RANGE = M_PI

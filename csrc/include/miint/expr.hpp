@@ -887,7 +887,30 @@ class ExprAdaptiveRegion {
 // and negates every value; a == b gives K zero rows with no launch; rows == 0 an empty result.
 // With AdaptSweepOptions::unbounded the shared range may be infinite: the rows run on t in
 // [0, 1] over the mapped integrand (AdaptRange above), the eval kernel replaced by its twin.
-// Left out: the final partition, per-row ranges, multi-rank runs.
+// Left out: the final partition, multi-rank runs.
+//
+// Per-row ranges (integrate_ranges): row r integrates over its own [a_r, b_r] to its own
+// max(atol, rtol |value of row r|), and is in every field, bit for bit, row 0 of
+// integrate({p_r}, 1, a_r, b_r, opt) with the same resolved panels and max_intervals. The
+// evaluation, prefix and scatter kernels are the first module's own; what reads the range has a
+// twin, generated into a second source (expr_adapt_sweep_ranges_source, which holds no
+// integrand: one text for every expression) that is compiled and loaded at an object's first
+// ranged call:
+//
+//   miint_asweep_init_ranges  miint_asweep_init with a and b of row r read from the device
+//                             arrays lo[r], hi[r] (lo[r] < hi[r]): w = hi[r] - lo[r], edges
+//                             lo[r] + (w j) / panels, the last one hi[r]; the same segments and
+//                             list of active rows
+//   miint_asweep_row_ranges   miint_asweep_row with W and atol of the wave's row read from the
+//                             device arrays width[r] (the host's hi_r - lo_r, as the shared
+//                             range's W is the host's hi - lo) and atol[r]; otherwise the same
+//                             text in the same order, so equal inputs give equal bits
+//
+// a_r > b_r integrates [b_r, a_r] and negates that row only. A row with a_r == b_r is 0 with
+// tol = atol, converged, no evaluations: the host leaves it out of the launch (the device sees
+// the other rows, compacted in order) and fills it in. NaN or infinite ends and a b_r - a_r
+// that overflows are refused up front, naming the row, and so is `unbounded`.
+// Left out: per-row infinite ranges.
 // ---------------------------------------------------------------------------------------
 constexpr uint64_t kAdaptSweepMaxTotalLimit = 1ull << 26;
 constexpr uint64_t kAdaptSweepInitialTotal = 65536;  // rows * panels the default aims at
@@ -930,6 +953,21 @@ std::string expr_adapt_sweep_compile(const std::string& expr, int nparams);
 // The eval kernels of the three infinite kinds (the rest of a round is expr_adapt_sweep_source's).
 std::string expr_adapt_sweep_unbounded_source(const std::string& expr, int nparams);
 std::string expr_adapt_sweep_unbounded_compile(const std::string& expr, int nparams);
+// adapt_sweep_check for per-row ranges: the same checks in the same words where they apply
+// (rows, nparams, param_count, max_total, panels, rows * max_intervals, the tolerances, the
+// depth), and a.size() == b.size() == rows, `unbounded` refused, every row's ends finite with a
+// finite b_r - a_r (the first offending row is named). No device needed.
+AdaptSweepOptions adapt_sweep_ranges_check(uint64_t rows, int nparams, uint64_t param_count,
+                                           const std::vector<double>& a,
+                                           const std::vector<double>& b,
+                                           const AdaptSweepOptions& opt);
+// The twins that read per-row ranges, and miint_acurve_prefix (ExprAdaptiveCurve below). No
+// integrand is in it: one source and one compile (cached) for every expression.
+std::string expr_adapt_sweep_ranges_source();
+std::string expr_adapt_sweep_ranges_compile();
+
+class ExprAdaptiveCurve;
+struct AdaptCurveResult;
 
 class ExprAdaptiveSweep {
  public:
@@ -945,18 +983,42 @@ class ExprAdaptiveSweep {
   // uploaded once, before the clock; the rounds' syncs and the host's reads are inside).
   double time(const std::vector<double>& params, uint64_t rows, double a, double b,
               const AdaptSweepOptions& opt, int iters);
+  // Row r on its own [a[r], b[r]] (the block above): a and b hold `rows` doubles each.
+  AdaptSweepResult integrate_ranges(const std::vector<double>& params, uint64_t rows,
+                                    const std::vector<double>& a, const std::vector<double>& b,
+                                    const AdaptSweepOptions& opt = {});
+  // `time` for per-row ranges: the rows and their ranges are uploaded once, before the clock.
+  double time_ranges(const std::vector<double>& params, uint64_t rows,
+                     const std::vector<double>& a, const std::vector<double>& b,
+                     const AdaptSweepOptions& opt, int iters);
   const std::string& expression() const { return expr_; }
   int nparams() const { return nparams_; }
 
  private:
+  friend class ExprAdaptiveCurve;
   struct Call {
     uint64_t rounds = 0, evals = 0, peak = 0;
   };
   void reserve(uint64_t max_total, uint64_t rows);
   void upload(const std::vector<double>& params);
   Call rounds(double lo, double hi, uint64_t rows, const AdaptSweepOptions& opt,
-              AdaptRange kind = AdaptRange::kFinite, double end = 0.0);
+              AdaptRange kind = AdaptRange::kFinite, double end = 0.0, bool ranged = false);
   void load_unbounded();
+  void load_ranges();
+  void reserve_curve(uint64_t points);
+  // The rows with a_r != b_r in order, their parameters, lo < hi and per-row atol uploaded;
+  // returns their indices. `atol` is null (opt.atol for every row) or one value per row.
+  std::vector<uint64_t> upload_ranges(const std::vector<double>& params, uint64_t rows,
+                                      const std::vector<double>& a, const std::vector<double>& b,
+                                      const double* atol, const AdaptSweepOptions& opt);
+  // integrate_ranges on options already resolved and checked; with `curve`, miint_acurve_prefix
+  // runs behind the last round, inside the events (every row is live then).
+  AdaptSweepResult run_ranges(const std::vector<double>& params, uint64_t rows,
+                              const std::vector<double>& a, const std::vector<double>& b,
+                              const double* atol, const AdaptSweepOptions& opt,
+                              AdaptCurveResult* curve);
+  void read_row(const unsigned long long* words, bool swapped, uint64_t k,
+                AdaptSweepResult* r) const;
   std::string expr_;
   int nparams_, device_;
   Stream stream_;
@@ -970,9 +1032,86 @@ class ExprAdaptiveSweep {
   DeviceBuffer<unsigned> seg_start_, seg_len_, next_len_;  // per row / per active slot
   DeviceBuffer<unsigned long long> state_;   // 16 words per row (expr_adaptive_sweep.cpp)
   PinnedBuffer<unsigned long long> record_;  // the next total and active count
+  uint64_t reserved_ranges_ = 0, reserved_curve_ = 0;
+  DeviceBuffer<double> ranges_;       // per-row ranges: lo, hi, width, atol, 4 x rows doubles
+  DeviceBuffer<double> curve_;        // F, err_est, tol, resabs: 4 x (M + 1) doubles
+  DeviceBuffer<unsigned> curve_bad_;  // the unconverged cells before each point: M + 1
+  PinnedBuffer<unsigned long long> curve_totals_;  // four doubles and the count
   Event e0_, e1_;
   detail::RtcModule module_;  // the last members: destroyed first (miint/expr_rtc.hpp)
   std::unique_ptr<detail::RtcModule> unbounded_;  // loaded at the first unbounded call
+  std::unique_ptr<detail::RtcModule> ranged_;     // loaded at the first ranged call
+};
+
+// ---------------------------------------------------------------------------------------
+// The running integral to a tolerance: F_j = the integral of f from x_0 to x_j on a caller's
+// grid x_0, ..., x_M (strictly increasing or strictly decreasing, 1 <= M <= 2^20), F_0 = 0.
+//
+// Cell c = [x_c, x_{c+1}] is row c of a ranged sweep with nparams = 0, to its own tolerance
+// max(atol_c, rtol |I_c|) with
+//   atol_c = (atol * |x_{c+1} - x_c|) / |x_M - x_0|
+// formed on the host in exactly that order: each cell is bitwise the single-row call on its
+// range with atol = atol_c. So |F_j - true| is estimated by err_est_j, the sum of the cells'
+// err_est before j, and that estimate is held to tol_j, the sum of their tol, which is at most
+// atol + rtol * (the integral of |f| up to x_j): for a positive density every point of the CDF,
+// the far tail included, is relatively accurate. converged_j: every cell before j converged. A
+// capped or non-finite cell marks the points from it onwards and no point before it.
+//
+//   miint_acurve_prefix  one workgroup of 256 threads behind the last round. per =
+//                        ceil(M / 256); thread t owns cells [t per, min((t + 1) per, M)) and
+//                        chains their value (negated first on a descending grid), err_est, tol
+//                        and resabs from 0.0 in index order, and counts its unconverged cells
+//                        (err_est <= tol, not capped, nonfinite == 0, as the host decides it);
+//                        thread 0 forms the 256 runs' exclusive prefixes P_t sequentially from
+//                        0.0; every thread walks its run again: F_{j+1} = P_t + (its chain
+//                        through cell j). M + 1 entries per array on the device, entry 0 zero;
+//                        the totals go to pinned host memory
+//
+// No floating-point atomic, no waiting between workgroups, a fixed order: bitwise
+// reproducible, and with M <= 256 (per = 1) the plain chain ((0 + I_0) + I_1) + ...
+//
+// Defaults (adapt_curve_check): panels = the largest power of two p <= 65536 with M p <= 65536,
+// at least 1 (a curve's cells are short already; the sweep's minimum of 16 is for whole
+// ranges); max_intervals = max_total / M. The capacity is dealt to the cells in equal parts: a
+// singular point inside a very fine grid caps its own cell.
+// Left out: parameter rows of curves, a cap shared between cells, infinite ends, the partition,
+// more than one rank.
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t kAdaptCurveMaxCells = 1ull << 20;
+
+struct AdaptCurveResult {
+  // per point, M + 1 entries; entry 0 is 0 (converged)
+  std::vector<double> x, value, err_est, tol, resabs;
+  std::vector<uint8_t> converged;
+  AdaptSweepResult cells;      // per cell, M rows
+  std::vector<double> atol_cell;  // atol_c
+  double total = 0.0, total_err_est = 0.0, total_tol = 0.0, total_resabs = 0.0;
+  uint64_t unconverged = 0;    // cells
+  uint64_t call_rounds = 0, call_evals = 0, peak = 0;
+  double device_ms = 0.0;      // the rounds and the prefix kernel
+  uint64_t points() const { return value.size(); }
+};
+
+// The options resolved (panels, max_intervals) after every refusal, no device needed: the grid
+// (2..2^20 + 1 finite points, strictly monotone, the first offending index named, a finite
+// x_M - x_0), `unbounded`, then adapt_sweep_ranges_check's on the resolved options.
+AdaptSweepOptions adapt_curve_check(const std::vector<double>& x, const AdaptSweepOptions& opt);
+// atol_c of every cell, in the documented order.
+std::vector<double> adapt_curve_atol(const std::vector<double>& x, double atol);
+
+class ExprAdaptiveCurve {
+ public:
+  ExprAdaptiveCurve(const std::string& expr, int device = 0);
+  ExprAdaptiveCurve(const ExprAdaptiveCurve&) = delete;
+  ExprAdaptiveCurve& operator=(const ExprAdaptiveCurve&) = delete;
+  AdaptCurveResult integrate(const std::vector<double>& x, const AdaptSweepOptions& opt = {});
+  // Device ms of miint_acurve_prefix alone over `iters` launches on a state of `cells` zero
+  // cells (what the kernel costs does not depend on the values).
+  double time_prefix(uint64_t cells, int iters);
+  const std::string& expression() const { return sweep_.expression(); }
+
+ private:
+  ExprAdaptiveSweep sweep_;
 };
 
 // ---------------------------------------------------------------------------------------

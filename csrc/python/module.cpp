@@ -1428,7 +1428,57 @@ PYBIND11_MODULE(_miint, m) {
         .def_readonly("peak", &R::peak)
         .def_readonly("device_ms", &R::device_ms)
         .def_readonly("range", &R::range);
+    using C = AdaptCurveResult;
+    py::class_<C>(m, "AdaptCurveResult",
+                  "per-point arrays (x, value, err_est, tol, resabs, converged; M + 1 entries), "
+                  "the per-cell AdaptSweepResult `cells` and atol_cell, the totals and the call")
+        .def(py::init<>())
+        .def_property_readonly("x", [f64](const C& r) { return f64(r.x); })
+        .def_property_readonly("value", [f64](const C& r) { return f64(r.value); })
+        .def_property_readonly("err_est", [f64](const C& r) { return f64(r.err_est); })
+        .def_property_readonly("tol", [f64](const C& r) { return f64(r.tol); })
+        .def_property_readonly("resabs", [f64](const C& r) { return f64(r.resabs); })
+        .def_property_readonly("converged", [flag](const C& r) { return flag(r.converged); })
+        .def_property_readonly("atol_cell", [f64](const C& r) { return f64(r.atol_cell); })
+        .def_readonly("cells", &C::cells)
+        .def_property_readonly("points", &C::points)
+        .def_readonly("total", &C::total)
+        .def_readonly("total_err_est", &C::total_err_est)
+        .def_readonly("total_tol", &C::total_tol)
+        .def_readonly("total_resabs", &C::total_resabs)
+        .def_readonly("unconverged", &C::unconverged)
+        .def_readonly("call_rounds", &C::call_rounds)
+        .def_readonly("call_evals", &C::call_evals)
+        .def_readonly("peak", &C::peak)
+        .def_readonly("device_ms", &C::device_ms);
+    m.def("adapt_curve_atol",
+          [f64](const std::vector<double>& x, double atol) {
+            return f64(adapt_curve_atol(x, atol));
+          },
+          py::arg("x"), py::arg("atol"),
+          "atol_c = (atol * |x[c + 1] - x[c]|) / |x[M] - x[0]| of every cell, in that order");
   }
+  m.attr("ADAPT_CURVE_MAX_CELLS") = kAdaptCurveMaxCells;
+  m.def("adapt_sweep_ranges_check", &adapt_sweep_ranges_check, py::arg("rows"),
+        py::arg("nparams"), py::arg("param_count"), py::arg("a"), py::arg("b"),
+        py::arg("options"),
+        "adapt_sweep_check for per-row ranges a[r], b[r]; returns the resolved options");
+  m.def("adapt_curve_check", &adapt_curve_check, py::arg("x"), py::arg("options"),
+        "raise, naming the first offending index or the numbers, unless ExprAdaptiveCurve takes "
+        "the grid; returns the options with a curve's panels and max_intervals resolved");
+  m.def("expr_adapt_sweep_ranges_source", &expr_adapt_sweep_ranges_source,
+        "source of the kernels that read per-row ranges and of the curve's prefix kernel");
+  m.def("expr_adapt_sweep_ranges_compile", compiled(&expr_adapt_sweep_ranges_compile),
+        "compile them for gfx950 with hipRTC (no device needed)");
+  py::class_<ExprAdaptiveCurve>(m, "ExprAdaptiveCurve",
+                                "F(x_j) = the integral of f from x_0 to x_j on a grid, every "
+                                "cell to a tolerance (hipRTC, gfx950)")
+      .def(py::init<const std::string&, int>(), py::arg("expr"), py::arg("device") = 0)
+      .def("integrate", &ExprAdaptiveCurve::integrate, py::arg("x"),
+           py::arg("options") = AdaptSweepOptions(), py::call_guard<py::gil_scoped_release>())
+      .def("time_prefix", &ExprAdaptiveCurve::time_prefix, py::arg("cells"), py::arg("iters"),
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("expression", &ExprAdaptiveCurve::expression);
   m.def("expr_adapt_sweep_unbounded_source", &expr_adapt_sweep_unbounded_source, py::arg("expr"),
         py::arg("nparams"),
         "source of the sweep's eval kernels of the infinite kinds for f(x, p0..p{nparams-1})");
@@ -1467,6 +1517,26 @@ PYBIND11_MODULE(_miint, m) {
              const std::vector<double> p = param_rows(params, e.nparams(), &rows);
              py::gil_scoped_release nogil;
              return e.time(p, rows, a, b, o, iters);
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"), py::arg("options"), py::arg("iters"))
+      .def("integrate_ranges",
+           [](ExprAdaptiveSweep& e, const ParamRows& params, const std::vector<double>& a,
+              const std::vector<double>& b, const AdaptSweepOptions& o) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             py::gil_scoped_release nogil;
+             return e.integrate_ranges(p, rows, a, b, o);
+           },
+           py::arg("params"), py::arg("a"), py::arg("b"),
+           py::arg("options") = AdaptSweepOptions(),
+           "row r on its own [a[r], b[r]]: a and b hold one number per row")
+      .def("time_ranges",
+           [](ExprAdaptiveSweep& e, const ParamRows& params, const std::vector<double>& a,
+              const std::vector<double>& b, const AdaptSweepOptions& o, int iters) {
+             uint64_t rows = 0;
+             const std::vector<double> p = param_rows(params, e.nparams(), &rows);
+             py::gil_scoped_release nogil;
+             return e.time_ranges(p, rows, a, b, o, iters);
            },
            py::arg("params"), py::arg("a"), py::arg("b"), py::arg("options"), py::arg("iters"))
       .def_property_readonly("expression", &ExprAdaptiveSweep::expression)

@@ -28,7 +28,9 @@ Capabilities of the reference (Excalibur1224/Cuda-v-MPI: riemann.cpp, cintegrate
     (``integrate_expr_oscillatory``, ``ops.kernels.quad_expr_osc``,
     ``riemann --expr ... --osc cos --omega W --rtol R``), and the same for f(x, p) over K parameter rows, each
     row to its own tolerance in shared rounds (``integrate_expr_adaptive_sweep``,
-    ``ops.kernels.quad_expr_sweep``, ``riemann --expr ... --params FILE --row-rtol R``), and
+    ``ops.kernels.quad_expr_sweep``, ``riemann --expr ... --params FILE --row-rtol R``), on a
+    shared range or on one range per row, and the running integral F(x_j) on a grid with every
+    cell to a tolerance (``integrate_expr_curve``, ``ops.kernels.quad_expr_curve``), and
     the double integral of f(x, y) over a rectangle to a tolerance
     (``integrate_expr2d_adaptive``, ``ops.kernels.quad_expr2d``,
     ``riemann --expr ... --ya AY --yb BY --area-rtol R``) or between two curves, y from
@@ -52,6 +54,7 @@ from .integrate import RunningResult, integrate_expr_running  # noqa: F401
 from .integrate import integrate_expr2d  # noqa: F401
 from .integrate import AdaptiveResult, integrate_expr_adaptive  # noqa: F401
 from .integrate import AdaptiveSweepResult, integrate_expr_adaptive_sweep  # noqa: F401
+from .integrate import CurveResult, integrate_expr_curve  # noqa: F401
 from .integrate import OscillatoryResult, integrate_expr_oscillatory  # noqa: F401
 from .integrate import Adaptive2DResult, integrate_expr2d_adaptive  # noqa: F401
 from .integrate import AdaptiveRegionResult, integrate_expr2d_region  # noqa: F401

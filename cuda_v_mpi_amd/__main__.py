@@ -216,6 +216,12 @@ def _json_ends(rec: dict) -> dict:
 def cmd_integrate(a) -> int:
     from . import Integrator
 
+    if (a.curve_rtol is not None or a.curve_atol is not None or a.points is not None
+            or a.at):
+        return _integrate_curve(a)
+    if a.ranges and a.row_rtol is None and a.row_atol is None:
+        raise SystemExit("integrate: --ranges gives the rows of a sweep to a tolerance their own "
+                         "ranges: it needs --row-rtol R / --row-atol T")
     if a.osc is not None or a.omega is not None or a.max_cycles is not None:
         return _integrate_osc(a)
     for flag, v in (("--a", a.a), ("--b", a.b)):
@@ -617,9 +623,17 @@ def _integrate_adaptive_sweep(a, lo: float, hi: float) -> int:
     opts = {k: v for k, v in (("rtol", a.row_rtol), ("atol", a.row_atol), ("panels", a.panels),
                               ("max_depth", a.max_depth), ("max_intervals", a.max_intervals),
                               ("max_total", a.max_total)) if v is not None}
+    if a.ranges and (a.a is not None or a.b is not None):
+        raise SystemExit("integrate: --ranges gives every row its own a and b: --a / --b do not "
+                         "go with it")
     m = native()
     try:
         rows = m.load_param_rows(a.params) if a.params else m.linspace_param_rows(a.linspace)
+        if a.ranges:
+            ends = _load_columns(a.ranges, 2, "--ranges", "a b")
+            if len(ends) != len(rows):
+                raise ValueError(f"--ranges {a.ranges}: {len(ends)} ranges for {len(rows)} rows")
+            lo, hi = [e[0] for e in ends], [e[1] for e in ends]
         r = integrate_expr_adaptive_sweep(a.expr, rows, lo, hi, **opts)
     except (ValueError, RuntimeError) as e:
         raise SystemExit(f"integrate: {e}") from None
@@ -635,6 +649,112 @@ def _integrate_adaptive_sweep(a, lo: float, hi: float) -> int:
     rec = _json_ends({k: (v.tolist() if hasattr(v, "tolist") else v)
                       for k, v in r.as_dict().items()})
     rec["rows"] = len(r.value)
+    rec["not_converged"] = missed
+    rec["value_bits"] = ["%016x" % int.from_bytes(pack("<d", float(v)), "little")
+                         for v in r.value]
+    print(json.dumps(rec))
+    return 0
+
+
+def _load_columns(path: str, columns: int, flag: str, what: str) -> list:
+    """The lines of a text file as tuples of ``columns`` numbers (blank lines and lines that
+    begin with # are skipped); anything else is refused, naming the line."""
+    out = []
+    try:
+        with open(path) as fh:
+            lines = fh.read().splitlines()
+    except OSError as e:
+        raise ValueError(f"{flag} {path}: {e.strerror}") from None
+    for n, line in enumerate(lines, 1):
+        words = line.split()
+        if not words or words[0].startswith("#"):
+            continue
+        try:
+            row = tuple(float(w) for w in words)
+        except ValueError:
+            row = ()
+        if len(row) != columns:
+            raise ValueError(f"{flag} {path}: line {n}: expected `{what}`, got '{line.strip()}'")
+        out.append(row)
+    return out
+
+
+def _integrate_curve(a) -> int:
+    """integrate --expr E --curve-rtol R / --curve-atol T with --a A --b B --points M or --at
+    FILE: the running integral on the grid, every cell to a tolerance (one GPU, one rank).
+    Whatever belongs to another mode is refused before anything runs."""
+    import math
+    import os
+
+    import numpy as np
+
+    from . import integrate_expr_curve
+
+    who = "--curve-rtol / --curve-atol"
+    if a.curve_rtol is None and a.curve_atol is None:
+        raise SystemExit(f"integrate: --points / --at are the grid of a running integral to a "
+                         f"tolerance: they need {who}")
+    if not a.expr:
+        raise SystemExit(f"integrate: {who} are the tolerance of an --expr running integral")
+    given = {"--n": a.n is not None, "--rule": a.rule is not None, "--rtol": a.rtol is not None,
+             "--atol": a.atol is not None, "--row-rtol": a.row_rtol is not None,
+             "--row-atol": a.row_atol is not None, "--ranges": bool(a.ranges),
+             "--area-rtol": a.area_rtol is not None, "--area-atol": a.area_atol is not None,
+             "--panels-y": a.panels_y is not None, "--y-lo": a.y_lo is not None,
+             "--y-hi": a.y_hi is not None, "--ya": a.ya is not None, "--yb": a.yb is not None,
+             "--ny": a.ny is not None, "--box": bool(a.box), "--osc": a.osc is not None,
+             "--omega": a.omega is not None, "--max-cycles": a.max_cycles is not None,
+             "--params": bool(a.params), "--linspace": bool(a.linspace)}
+    for flag, on in given.items():
+        if on:
+            raise SystemExit(f"integrate: {who} are the tolerance of a running integral on a "
+                             f"grid: {flag} does not go with them")
+    _no_lattice_flags(a)
+    if a.device == "cpu" or a.backend != "hip":
+        which = "--device cpu" if a.device == "cpu" else f"--backend {a.backend}"
+        raise SystemExit(f"integrate: {who} have no host engine: {which} does not go with them")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"integrate: {who} run as one rank: a rank environment "
+                         f"(WORLD_SIZE = {os.environ['WORLD_SIZE']}) does not go with them")
+    if a.at:
+        if a.a is not None or a.b is not None or a.points is not None:
+            raise SystemExit("integrate: --at FILE is the whole grid: --a / --b / --points do not "
+                             "go with it")
+    else:
+        if a.a is None or a.b is None or a.points is None:
+            raise SystemExit(f"integrate: {who} need a grid: --a A --b B --points M, or --at FILE")
+        if math.isinf(a.a) or math.isinf(a.b):
+            raise SystemExit(f"integrate: {who} take a finite grid: --a {a.a} --b {a.b} has an "
+                             "infinite end")
+        if a.points < 1:
+            raise SystemExit(f"integrate: --points {a.points} must be at least 1")
+    opts = {k: v for k, v in (("rtol", a.curve_rtol), ("atol", a.curve_atol),
+                              ("panels", a.panels), ("max_depth", a.max_depth),
+                              ("max_intervals", a.max_intervals), ("max_total", a.max_total))
+            if v is not None}
+    try:
+        if a.at:
+            x = np.array([p[0] for p in _load_columns(a.at, 1, "--at", "x")], dtype=np.float64)
+        else:  # x_j = a + ((b - a) j) / M, the last one b: the adaptive rules' edges
+            j = np.arange(a.points + 1, dtype=np.float64)
+            x = a.a + ((a.b - a.a) * j) / float(a.points)
+            x[-1] = a.b
+        r = integrate_expr_curve(a.expr, x, **opts)
+    except (ValueError, RuntimeError) as e:
+        raise SystemExit(f"integrate: {e}") from None
+    missed = int((~r.cells["converged"]).sum())
+    if missed:
+        print(f"integrate: not converged: {missed} of {len(r.cells['value'])} cells, the first "
+              f"one cell {int(np.flatnonzero(~r.cells['converged'])[0])} (see converged per point "
+              "and capped, nonfinite and forced per cell with --json)", file=sys.stderr)
+    if not a.json:
+        for xj, v, e in zip(r.x, r.value, r.err_est):
+            print(f"{xj:.17g} {v:.17g} {e:.3g}")
+        return 0
+    pack = __import__("struct").pack
+    rec = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.as_dict().items()}
+    rec["cells"] = {k: v.tolist() for k, v in r.cells.items()}
+    rec["points"] = len(r.value)
     rec["not_converged"] = missed
     rec["value_bits"] = ["%016x" % int.from_bytes(pack("<d", float(v)), "little")
                          for v in r.value]
@@ -804,6 +924,20 @@ def main(argv=None) -> int:
     ig.add_argument("--row-atol", type=float, default=None)
     ig.add_argument("--max-total", type=int, default=None, help="--row-rtol / --row-atol: "
                     "intervals of all rows together (2^22)")
+    ig.add_argument("--ranges", default="", metavar="FILE", help="--row-rtol / --row-atol: a "
+                    "file of K lines `a b`, row r integrated over its own finite [a_r, b_r] "
+                    "(instead of --a / --b); a_r > b_r negates the row, a_r == b_r gives 0")
+    ig.add_argument("--curve-rtol", type=float, default=None, help="with --expr: the running "
+                    "integral F(x_j) from x_0 on a grid, either --a A --b B --points M (M equal "
+                    "cells) or --at FILE (one grid point per line, strictly increasing or "
+                    "decreasing); every cell to max(its share of curve-atol by length, "
+                    "curve-rtol |its integral|). Prints `x F err_est` lines, or --json with the "
+                    "arrays (one GPU, one rank); --panels and --max-intervals are then per cell")
+    ig.add_argument("--curve-atol", type=float, default=None)
+    ig.add_argument("--points", type=int, default=None, metavar="M",
+                    help="--curve-rtol / --curve-atol: M equal cells on [a, b]")
+    ig.add_argument("--at", default="", metavar="FILE",
+                    help="--curve-rtol / --curve-atol: the grid, one point per line")
     ig.add_argument("--box", default="", help="with --expr over x0, x1, ...: A0:B0,A1:B1,..., the "
                     "integral over the box by a randomly shifted lattice rule (--m M, or --rtol / "
                     "--atol for the walk over M)")

@@ -848,13 +848,25 @@ def integrate_expr_adaptive_sweep(expr: str, params, a: float, b: float, rtol: f
     are per row (0: derived), ``max_total`` bounds all rows' intervals together.
     ``backend="hip"``: the hipRTC-compiled gfx950 kernels (``ops.kernels.quad_expr_sweep``),
     one GPU. ``backend="cpu"``: the numpy model (``utils.adaptive_quad.adaptive_sweep_model``)
-    on ``expr_torch``'s subset of expressions; needs no GPU. One rank, one shared range, whose
-    ends may be infinite as for ``integrate_expr_adaptive``."""
-    from .utils.adaptive_quad import SWEEP_ROW_FIELDS, adaptive_sweep_model
+    on ``expr_torch``'s subset of expressions; needs no GPU. One rank. A shared range (numbers
+    for ``a`` and ``b``) may have infinite ends as for ``integrate_expr_adaptive``. With a
+    sequence of K numbers for ``a`` or ``b`` (a number beside one is repeated) row r runs on
+    its own finite [a[r], b[r]], bitwise as the one-row call on that range would; the result's
+    ``a`` and ``b`` are then arrays."""
+    from .utils.adaptive_quad import (SWEEP_ROW_FIELDS, adaptive_sweep_model,
+                                      adaptive_sweep_ranges_model)
 
-    a, b = float(a), float(b)
+    ranged = np.ndim(a) != 0 or np.ndim(b) != 0
+    if ranged:
+        rows = len(params)
+        a, b = (np.asarray(v, dtype=np.float64) if np.ndim(v) != 0 else np.full(rows, float(v))
+                for v in (a, b))
+    else:
+        a, b = float(a), float(b)
     opts = dict(rtol=rtol, atol=atol, panels=int(panels), max_depth=int(max_depth),
-                max_intervals=int(max_intervals), max_total=int(max_total), unbounded=True)
+                max_intervals=int(max_intervals), max_total=int(max_total))
+    if not ranged:
+        opts["unbounded"] = True
     if backend == "hip":
         from .ops import kernels
 
@@ -868,12 +880,83 @@ def integrate_expr_adaptive_sweep(expr: str, params, a: float, b: float, rtol: f
             return expr_torch(expr, torch.from_numpy(x), names=names).numpy()
 
         t0 = time.perf_counter()
-        r = adaptive_sweep_model(f, params, a, b, **opts)
+        r = (adaptive_sweep_ranges_model if ranged else adaptive_sweep_model)(f, params, a, b,
+                                                                              **opts)
         ms = (time.perf_counter() - t0) * 1e3
+        r.setdefault("range", "finite")
         fields = {k: r[k] for k in SWEEP_ROW_FIELDS + _ADAPT_SWEEP_CALL_FIELDS}
     else:
         raise ValueError("integrate_expr_adaptive_sweep backend must be 'hip' or 'cpu'")
     return AdaptiveSweepResult(**fields, device_ms=ms, expr=expr, a=a, b=b, backend=backend)
+
+
+@dataclasses.dataclass
+class CurveResult:
+    """Per point (numpy arrays of M + 1 entries; entry 0 is the start: 0, converged), the cells
+    (``AdaptiveSweepResult``-like per-cell arrays in ``cells``), then the call."""
+    x: "np.ndarray"
+    value: "np.ndarray"        # F_j, the integral from x[0] to x[j]
+    err_est: "np.ndarray"      # the sum of the cells' err_est before j
+    tol: "np.ndarray"          # the sum of the cells' tolerances before j: err_est is held to it
+    resabs: "np.ndarray"
+    converged: "np.ndarray"    # bool: every cell before j converged
+    cells: dict                # per cell: the fields of ``AdaptiveSweepResult``'s rows
+    atol_cell: "np.ndarray"    # (atol * |x[c + 1] - x[c]|) / |x[M] - x[0]|
+    total: float               # F_M
+    call_rounds: int
+    call_evals: int
+    peak: int
+    device_ms: float           # the rounds and the prefix (hip) or the model's run (cpu), in ms
+    expr: str
+    backend: str
+
+    def as_dict(self) -> dict:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+
+
+_CURVE_POINT_FIELDS = ("x", "value", "err_est", "tol", "resabs", "converged", "atol_cell",
+                       "total", "call_rounds", "call_evals", "peak")
+
+
+def integrate_expr_curve(expr: str, x, rtol: float = 1e-10, atol: float = 0.0, panels: int = 0,
+                         max_depth: int = 60, max_intervals: int = 0, max_total: int = 1 << 22,
+                         backend: str = "hip") -> CurveResult:
+    """The running integral of f to a tolerance: F_j, the integral from x[0] to x[j], at every
+    point of the caller's grid ``x`` (M + 1 strictly increasing or strictly decreasing numbers;
+    F_0 = 0). Each cell [x[c], x[c + 1]] is integrated adaptively to max(atol_c, rtol * |its
+    integral|) with atol_c its share of ``atol`` by length, so ``err_est[j]`` (the estimate of
+    |F_j - truth|) is held to ``tol[j]`` <= atol + rtol * (the integral of |f| up to x[j]): a
+    CDF is relatively accurate at every point, its far tail included. ``converged[j]`` says
+    that every cell before x[j] converged; a capped or non-finite cell marks the points from it
+    onwards and changes no point before it. ``panels`` and ``max_intervals`` are per cell (0:
+    derived); ``max_total`` is dealt to the cells in equal parts, so a singular point inside a
+    very fine grid caps its own cell: give such grids a larger ``max_total`` or fewer points.
+    ``backend="hip"``: ``ops.kernels.quad_expr_curve``, one GPU. ``backend="cpu"``: the numpy
+    model (``utils.adaptive_quad.adaptive_curve_model``) on ``expr_torch``'s subset of
+    expressions; needs no GPU."""
+    from .utils.adaptive_quad import SWEEP_ROW_FIELDS, adaptive_curve_model
+
+    opts = dict(rtol=rtol, atol=atol, panels=int(panels), max_depth=int(max_depth),
+                max_intervals=int(max_intervals), max_total=int(max_total))
+    if backend == "hip":
+        from .ops import kernels
+
+        r = kernels.quad_expr_curve(expr, x, **opts)[0]
+        fields = {k: getattr(r, k) for k in _CURVE_POINT_FIELDS}
+        cells = {k: getattr(r.cells, k) for k in SWEEP_ROW_FIELDS}
+        ms = r.device_ms
+    elif backend == "cpu":
+        def f(t):
+            return expr_torch(expr, torch.from_numpy(np.ascontiguousarray(t))).numpy()
+
+        t0 = time.perf_counter()
+        r = adaptive_curve_model(f, x, **opts)
+        ms = (time.perf_counter() - t0) * 1e3
+        fields = {k: r[k] for k in _CURVE_POINT_FIELDS}
+        cells = {k: r["cells"][k] for k in SWEEP_ROW_FIELDS}
+    else:
+        raise ValueError("integrate_expr_curve backend must be 'hip' or 'cpu'")
+    return CurveResult(**fields, cells=cells, device_ms=ms, expr=expr, backend=backend)
 
 
 @dataclasses.dataclass

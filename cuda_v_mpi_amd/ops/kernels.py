@@ -657,13 +657,27 @@ def quad_expr_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
     forced, nonfinite, capped; for the call call_rounds, call_evals, peak, device_ms) and the
     first three of its per-row arrays as 1-D device tensors (fp64, fp64, bool). No rows: empty
     results, nothing compiled or launched. With ``unbounded`` the shared a and b may be infinite,
-    as for ``quad_expr``; the result's ``range`` names the kind."""
+    as for ``quad_expr``; the result's ``range`` names the kind.
+
+    Per-row ranges: with a sequence of K numbers for ``a`` or ``b`` (a scalar beside one is
+    repeated) row r runs on its own [a[r], b[r]], bitwise as the one-row call on that range
+    would; a[r] > b[r] negates that row, a[r] == b[r] gives it 0. Such ranges are finite."""
+    import numpy as np
+
     m = native()
     p = _param_rows(params)
     rows, nparams = p.shape
     opt = m.AdaptSweepOptions(float(rtol), float(atol), int(panels), int(max_depth),
                               int(max_intervals), int(max_total), bool(unbounded))
-    m.adapt_sweep_check(int(rows), int(nparams), int(p.size), float(a), float(b), opt)
+    ranged = np.ndim(a) != 0 or np.ndim(b) != 0
+    if ranged:
+        lo, hi = (v if np.ndim(v) != 0 else np.full(rows, float(v)) for v in (a, b))
+        lo, hi = (np.asarray(v, dtype=np.float64) for v in (lo, hi))
+        if lo.ndim != 1 or hi.ndim != 1:
+            raise ValueError("a and b must be numbers or 1-D sequences of one number per row")
+        m.adapt_sweep_ranges_check(int(rows), int(nparams), int(p.size), lo, hi, opt)
+    else:
+        m.adapt_sweep_check(int(rows), int(nparams), int(p.size), float(a), float(b), opt)
     dev = _device()
     if rows == 0:
         r = m.AdaptSweepResult()
@@ -672,9 +686,48 @@ def quad_expr_sweep(expr: str, params, a: float, b: float, rtol: float = 1e-10,
         es = _EXPR_ADAPT_SWEEP_CACHE.get(key)
         if es is None:
             es = _EXPR_ADAPT_SWEEP_CACHE[key] = m.ExprAdaptiveSweep(expr, int(nparams), dev.index)
-        r = es.integrate(p, float(a), float(b), opt)
+        r = (es.integrate_ranges(p, lo, hi, opt) if ranged
+             else es.integrate(p, float(a), float(b), opt))
     return (r, torch.as_tensor(r.value, dtype=torch.float64).to(dev),
             torch.as_tensor(r.err_est, dtype=torch.float64).to(dev),
+            torch.as_tensor(r.converged, dtype=torch.bool).to(dev))
+
+
+_EXPR_ADAPT_CURVE_CACHE: dict = {}
+
+
+def quad_expr_curve(expr: str, x, rtol: float = 1e-10, atol: float = 0.0, panels: int = 0,
+                    max_depth: int = 60, max_intervals: int = 0, max_total: int = 1 << 22):
+    """The running integral F_j of f from x[0] to x[j] on the caller's grid ``x`` (M + 1
+    strictly increasing or strictly decreasing points), every cell [x[c], x[c + 1]] to its own
+    tolerance max(atol_c, rtol * |its integral|), atol_c = (atol * |x[c + 1] - x[c]|) /
+    |x[M] - x[0]|: the cells are the rows of a ranged sweep (``quad_expr_sweep``), each bitwise
+    the one-row call on its range, and F is their prefix in a fixed order, formed on the device
+    (miint/expr.hpp, ExprAdaptiveCurve). ``panels`` and ``max_intervals`` are per cell (0: the
+    largest power of two with M * panels <= 65536, at least 1; ``max_total`` / M). Returns
+    ``(result, values, err_est, tol, converged)``: the native AdaptCurveResult (per-point x,
+    value, err_est, tol, resabs, converged; ``cells``, the per-cell AdaptSweepResult;
+    ``atol_cell``; total, total_err_est, total_tol, total_resabs, unconverged; call_rounds,
+    call_evals, peak, device_ms) and four of its per-point arrays as 1-D device tensors (fp64,
+    fp64, fp64, bool) of M + 1 entries."""
+    import numpy as np
+
+    m = native()
+    grid = np.asarray(x, dtype=np.float64)
+    if grid.ndim != 1:
+        raise ValueError("x must be a 1-D sequence of grid points")
+    opt = m.AdaptSweepOptions(float(rtol), float(atol), int(panels), int(max_depth),
+                              int(max_intervals), int(max_total), False)
+    m.adapt_curve_check(grid, opt)
+    dev = _device()
+    key = (expr, dev.index)
+    ec = _EXPR_ADAPT_CURVE_CACHE.get(key)
+    if ec is None:
+        ec = _EXPR_ADAPT_CURVE_CACHE[key] = m.ExprAdaptiveCurve(expr, dev.index)
+    r = ec.integrate(grid, opt)
+    return (r, torch.as_tensor(r.value, dtype=torch.float64).to(dev),
+            torch.as_tensor(r.err_est, dtype=torch.float64).to(dev),
+            torch.as_tensor(r.tol, dtype=torch.float64).to(dev),
             torch.as_tensor(r.converged, dtype=torch.bool).to(dev))
 
 

@@ -305,3 +305,148 @@ def adaptive_sweep_model(f, params, a: float, b: float, rtol: float = 1e-10, ato
     out["range"] = range_kind(a, b)
     out.update(res)
     return out
+
+
+# ------------------------------------------------------------------ per-row ranges, curves
+def check_sweep_ranges(rows: int, nparams: int, param_count: int, a, b, rtol: float = 1e-10,
+                       atol: float = 0.0, panels: int = 0, max_depth: int = 60,
+                       max_intervals: int = 0, max_total: int = 1 << 22,
+                       unbounded: bool = False) -> dict:
+    """The refusals of ``adapt_sweep_ranges_check``, with its wording and in its order; returns
+    ``panels`` and ``max_intervals`` with their zeros resolved."""
+    what = "adaptive sweep: "
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.shape != (rows,) or b.shape != (rows,):
+        raise ValueError(f"{what}{a.size} lower and {b.size} upper ends for {rows} rows")
+    if unbounded:
+        raise ValueError(f"{what}per-row ranges are finite: unbounded takes one shared range")
+    res = check_sweep_options(rows, nparams, param_count, 0.0, 1.0, rtol, atol, panels,
+                              max_depth, max_intervals, max_total)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ok = np.isfinite(a) & np.isfinite(b) & np.isfinite(b - a)
+    if not ok.all():
+        r = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"{what}row {r}: a = {a[r]:.17g} and b = {b[r]:.17g} must be finite, "
+                         "and b - a too")
+    return res
+
+
+def adaptive_sweep_ranges_model(f, params, a, b, rtol: float = 1e-10, atol=0.0,
+                                panels: int = 0, max_depth: int = 60, max_intervals: int = 0,
+                                max_total: int = 1 << 22) -> dict:
+    """``adaptive_sweep_model`` with row r on its own [a[r], b[r]]: ``adaptive_model`` row by row
+    on the options resolved for all rows. ``atol`` is one number, or one per row (a curve's
+    atol_c). A row with a[r] == b[r] is 0 with tol = atol, converged, no evaluations. Returns
+    what ``adaptive_sweep_model`` returns, ``range`` aside."""
+    p = np.asarray(params, dtype=np.float64)
+    if p.ndim == 1 and p.size == 0:
+        p = p.reshape(0, 0)
+    if p.ndim != 2:
+        raise ValueError("params must be K rows of nparams numbers (2-D)")
+    rows, nparams = p.shape
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    atols = np.broadcast_to(np.asarray(atol, dtype=np.float64), (rows,))
+    res = check_sweep_ranges(rows, nparams, p.size, a, b, rtol,
+                             float(atols.max()) if rows else 0.0, panels, max_depth,
+                             max_intervals, max_total)
+    runs, sizes = [], []
+    for k in range(rows):
+        seen: list = []
+
+        def counted(x, row=p[k], seen=seen):
+            seen.append(x.shape[0])
+            return f(x, *row)
+
+        runs.append(adaptive_model(counted, float(a[k]), float(b[k]), rtol=rtol,
+                                   atol=float(atols[k]), panels=res["panels"],
+                                   max_depth=max_depth, max_intervals=res["max_intervals"]))
+        sizes.append(seen)
+    out = {}
+    kinds = dict(converged=bool, capped=bool, value=np.float64, err_est=np.float64,
+                 resabs=np.float64, tol=np.float64)
+    for key in SWEEP_ROW_FIELDS:
+        out[key] = np.array([r[key] for r in runs], dtype=kinds.get(key, np.int64))
+    out["peak_row"] = np.array([r["peak"] for r in runs], dtype=np.int64)
+    depth = max((len(v) for v in sizes), default=0)
+    whole = [sum(v[t] for v in sizes if t < len(v)) for t in range(depth)]
+    out["call_rounds"] = int(out["rounds"].max()) if rows else 0
+    out["call_evals"] = int(out["evals"].sum())
+    out["peak"] = max(whole, default=0)
+    out.update(res)
+    return out
+
+
+CURVE_MAX_CELLS = 1 << 20
+
+
+def curve_default_panels(cells: int) -> int:
+    """A curve's ``panels = 0``: the largest power of two p <= 65536 with cells * p <= 65536, at
+    least 1."""
+    p = DEFAULTS["panels"]
+    while p > 1 and cells * p > SWEEP_INITIAL_TOTAL:
+        p >>= 1
+    return p
+
+
+def check_curve(x, rtol: float = 1e-10, atol: float = 0.0, panels: int = 0, max_depth: int = 60,
+                max_intervals: int = 0, max_total: int = 1 << 22) -> dict:
+    """The refusals of ``adapt_curve_check``, with its wording; returns the resolved ``panels``
+    and ``max_intervals``."""
+    what = "adaptive curve: "
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1 or not 2 <= x.size <= CURVE_MAX_CELLS + 1:
+        raise ValueError(f"{what}{x.size} points: the grid must hold 2..2^20 + 1")
+    if not np.isfinite(x).all():
+        i = int(np.flatnonzero(~np.isfinite(x))[0])
+        raise ValueError(f"{what}x[{i}] = {x[i]:.17g} must be finite")
+    bad = ~(x[1:] > x[:-1]) if x[1] > x[0] else ~(x[1:] < x[:-1])
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0]) + 1
+        raise ValueError(f"{what}x[{i}] = {x[i]:.17g} after x[{i - 1}] = {x[i - 1]:.17g}: the "
+                         "grid must be strictly increasing or strictly decreasing")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(x[-1] - x[0]):
+            raise ValueError(f"{what}x[0] = {x[0]:.17g} and x[M] = {x[-1]:.17g}: x[M] - x[0] "
+                             "must be finite")
+    cells = x.size - 1
+    if panels == 0:
+        panels = curve_default_panels(cells)
+    return check_sweep_options(cells, 0, 0, 0.0, 1.0, rtol, atol, panels, max_depth,
+                               max_intervals, max_total)
+
+
+def curve_atol(x, atol: float) -> np.ndarray:
+    """atol_c = (atol * |x[c + 1] - x[c]|) / |x[M] - x[0]|, in that order."""
+    x = np.asarray(x, dtype=np.float64)
+    return (atol * np.abs(np.diff(x))) / abs(x[-1] - x[0])
+
+
+def adaptive_curve_model(f, x, rtol: float = 1e-10, atol: float = 0.0, panels: int = 0,
+                         max_depth: int = 60, max_intervals: int = 0,
+                         max_total: int = 1 << 22) -> dict:
+    """The running integral F_j of f from x[0] to x[j] by the rule of ExprAdaptiveCurve: cell c
+    is ``adaptive_model`` on [x[c], x[c + 1]] with atol_c, and the per-point value, err_est, tol
+    and resabs are the cells' running sums (numpy's ``cumsum`` here, the device's fixed order
+    there), ``converged`` whether every cell before the point converged. Returns those arrays
+    (M + 1 entries), ``cells`` (the ranged sweep model's dict), ``atol_cell``, ``total`` and
+    the call's ``call_rounds``, ``call_evals`` and ``peak``."""
+    x = np.asarray(x, dtype=np.float64)
+    res = check_curve(x, rtol, atol, panels, max_depth, max_intervals, max_total)
+    atol_c = curve_atol(x, atol)
+    cells = adaptive_sweep_ranges_model(lambda t: f(t), np.zeros((x.size - 1, 0)), x[:-1], x[1:],
+                                        rtol=rtol, atol=atol_c, panels=res["panels"],
+                                        max_depth=max_depth,
+                                        max_intervals=res["max_intervals"], max_total=max_total)
+
+    def running(v):
+        return np.concatenate([[0.0], np.cumsum(v)])
+
+    out = dict(x=x, value=running(cells["value"]), err_est=running(cells["err_est"]),
+               tol=running(cells["tol"]), resabs=running(cells["resabs"]),
+               converged=np.concatenate([[True], np.cumsum(~cells["converged"]) == 0]),
+               cells=cells, atol_cell=atol_c)
+    out["total"] = float(out["value"][-1])
+    for key in ("call_rounds", "call_evals", "peak"):
+        out[key] = cells[key]
+    out.update(res)
+    return out
